@@ -8,6 +8,17 @@ the reference's per-frame early exit, Eb/N0 = 2 dB with the reference noise
 convention (sigma = sqrt(10^(-EbN0/10)), apps/ldpc_lapack.cpp:635-642).
 
   python bench.py [--gpus N --steps K --warmup W] [--inflight D] [--strong]
+                   [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it makes
+the data, runs the timed path untimed for --preroll-ms (so the K steps see the
+GPU's steady clock), warms up, times the K steps, writes the last timed step's
+outputs if --dump-outputs is given, and prints the JSON line.  --full adds
+everything else the line can hold: the GPU variants (config 4, config 5, the
+block, the other methods / precisions, one batch in flight), measured before
+the headline as they always were, the CPU baseline and the parity counts
+against the oracle, the all-rank parity of an N-rank run, and the --sweep-*
+tables.
 
 Data are made on the GPU before timing: Philox bits (ldpc_random_bits) ->
 systematic GF(2) encode (ldpc_encode_device) -> BPSK + AWGN
@@ -83,6 +94,19 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--inflight", type=int, default=4,
                     help="batches in flight (consecutive steps on alternating streams)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the GPU "
+                         "variants, the CPU baseline, parity against the oracle, the sweeps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (packed bytes, iteration "
+                         "counts, syndrome weights of every frame of its batch) to DIR/<name>.npy "
+                         "as float32")
+    # measured on an MI355X at --steps 20 --warmup 5, three runs each: after the
+    # --full variants 1243-1278 Mbit/s; preroll 0: 1070-1103, 50 ms: 1167-1174,
+    # 300 ms: 1332-1334, 1 s: 1311-1324, 3 s: 1245-1264.  At --steps 1000 all
+    # agree within 1 % (1413-1425).
+    ap.add_argument("--preroll-ms", type=float, default=300.0,
+                    help="plain run: the timed path run untimed for this long before the warmup")
     ap.add_argument("--strong", action="store_true",
                     help="N > 1: split one global batch over the ranks (default: weak scaling)")
     ap.add_argument("--code", choices=["default", "dvbs2"], default="default",
@@ -116,7 +140,10 @@ def parse(argv=None):
                     help="comma list of B: config 5 (syndrome check every 5 iterations, mixed "
                          "Eb/N0 0..4 dB per frame) latency/throughput table to stderr")
     ap.add_argument("--pmc-json", default=os.path.join(REPO, "profiles", "pmc_counters.json"))
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full and (args.sweep_batch or args.sweep_inflight or args.sweep_config5):
+        ap.error("the --sweep-* tables are part of --full")
+    return args
 
 
 # --------------------------------------------------------------------------
@@ -292,7 +319,8 @@ def time_ring(dec, torch, inputs, B, method, iters, et, prec, steps, warmup, dis
     before the timed session begins to one recorded after it ends (the
     launch follows the first and the second follows the launch),
     per_launch_ms = span_ms / steps (per batch), outs[d] = (packed, iters,
-    synd) of the last timed batch of inputs[d]."""
+    synd) of the last timed batch of inputs[d], last_out = those of the last
+    timed step."""
     D = len(inputs)
     dev = inputs[0].device
     # the session's stream (torch's default stream is the null stream, which
@@ -330,7 +358,8 @@ def time_ring(dec, torch, inputs, B, method, iters, et, prec, steps, warmup, dis
     span = e0.elapsed_time(e1) if steps else 0.0
     outs = [pool[last[d]] if d in last else pool[0] for d in range(D)]
     return dict(wall=wall, span_ms=span, per_launch_ms=span / max(1, steps),
-                iters=outs[0][1].cpu().numpy(), outs=outs, ring=dec.ring_info())
+                iters=outs[0][1].cpu().numpy(), outs=outs, ring=dec.ring_info(),
+                last_out=pool[warmup + steps - 1] if steps else None)
 
 
 def time_decoder(dec, torch, inputs, B, method, iters, et, prec, steps, warmup, dist=None,
@@ -341,7 +370,7 @@ def time_decoder(dec, torch, inputs, B, method, iters, et, prec, steps, warmup, 
     the device time from the first launch's start (a HIP event on the first
     timed step's stream, which each other stream waits for before its first
     launch) to the last launch's end (one event per stream) and per_launch_ms = span_ms / steps.  outs[d] = (packed, iters,
-    synd) of the last decode of batch d."""
+    synd) of the last decode of batch d, last_out = those of the last step."""
     D = max(1, inflight)
     dev = inputs[0].device
     if streams is None:
@@ -395,7 +424,8 @@ def time_decoder(dec, torch, inputs, B, method, iters, et, prec, steps, warmup, 
     span = max(e0.elapsed_time(e) for e in ends) if marks else 0.0
     return dict(wall=wall, span_ms=span, per_launch_ms=span / max(1, steps),
                 iters=outs[0][1].cpu().numpy(), outs=outs,
-                streams_distinct=len(set(s.cuda_stream for s in streams)))
+                streams_distinct=len(set(s.cuda_stream for s in streams)),
+                last_out=outs[(warmup + steps - 1) % D] if steps else None)
 
 
 # --------------------------------------------------------------------------
@@ -772,6 +802,42 @@ def gpu_variants(L, torch, dec, args, dev, inputs, B, D, prec, dvb, world, rank)
     return res
 
 
+def preroll(timer, dec, torch, inputs, B, args, prec, D, ms):
+    """A plain run's stand-in for the variants that --full measures before the
+    headline: the timed path itself (same method, precision and batches in
+    flight), untimed, for at least `ms` milliseconds, so the warmup and the K
+    steps start on a GPU whose clock has ramped (profiles/round1/
+    warmup_clock.txt; the figures beside --preroll-ms) and whose output
+    buffers come from memory the process has used before.  Nothing is
+    reported from it."""
+    if ms > 0:
+        time_variant(timer, dec, torch, inputs, B, args.method, args.iters, args.et_period, prec,
+                     8, 0, D, min_s=ms * 1e-3)
+
+
+DUMP_BYTES = 64 << 20  # the most --dump-outputs writes, all files together
+
+
+def dump_outputs(path, named, seed):
+    """--dump-outputs: every (name, device tensor) of `named` -- the outputs
+    of the last timed step, one row per frame -- as path/<name>.npy in
+    float32 (exact for the bytes and the counts they hold).  Above DUMP_BYTES
+    in all, the same seeded sample of the frames is written of every array and
+    the frames' numbers go to path/frame_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrs = [(n, t.cpu().numpy()) for n, t in named]
+    rows = arrs[0][1].shape[0]
+    total = sum(4 * a.size for _, a in arrs)
+    if total > DUMP_BYTES:
+        per_row = total // rows + 8  # + the frame's number (float64)
+        keep = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(
+            rows, size=max(1, (DUMP_BYTES - 4096) // per_row), replace=False))
+        arrs = [(n, a[keep]) for n, a in arrs] + [("frame_index", keep)]
+    for n, a in arrs:
+        np.save(os.path.join(path, n + ".npy"),
+                np.ascontiguousarray(a, dtype=np.float64 if n == "frame_index" else np.float32))
+
+
 def relaunch_distributed(args):
     """`python bench.py --gpus N` (N > 1) outside torchrun: run torchrun as a
     child process (no exec; nothing has touched the GPU yet) and return its
@@ -878,7 +944,8 @@ def main():
     inputs = [synth_device(L, torch, dec, B, args.ebn0, args.seed + 7919 * rank + 104729 * j,
                            dev)[0] for j in range(D)]
     torch.cuda.synchronize(dev)
-    sweeps(L, torch, dec, args, dev)
+    if args.full:
+        sweeps(L, torch, dec, args, dev)
 
     # several batches in flight: the throughput launch mode (4 waves per CU per
     # launch, four-waves-per-SIMD build, no issue-priority management;
@@ -892,12 +959,17 @@ def main():
     # GPU that has been busy for a while (its clock ramps from ~2.0 to
     # ~2.33 GHz over the first ~20 ms of work, profiles/round1/
     # warmup_clock.txt) and every rank arrives in the same state.  Their CPU
-    # checks run after the headline.
-    pre = gpu_variants(L, torch, dec, args, dev, inputs, B, D, prec, dvb, world, rank)
+    # checks run after the headline.  A plain run (no --full) measures none
+    # of them and runs the timed path itself for a moment instead (preroll).
     # small codes: the frame ring (one launch per timed region, frames of all
     # batches from one queue); large codes (config 4's pipeline): a launch per
     # batch
     timer = time_decoder if dvb else time_ring
+    if args.full:
+        pre = gpu_variants(L, torch, dec, args, dev, inputs, B, D, prec, dvb, world, rank)
+    else:
+        pre = dict(variants={}, serial=None, outs={}, config4_check=None, config5_check=None)
+        preroll(timer, dec, torch, inputs, B, args, prec, D, args.preroll_ms)
     r = timer(dec, torch, inputs, B, args.method, args.iters, args.et_period, prec,
               args.steps, args.warmup, dist, inflight=D)
     wall = r["wall"]
@@ -916,6 +988,10 @@ def main():
     if rank != 0:
         dist.destroy_process_group()
         return
+    if args.dump_outputs:  # rank 0's own last timed step
+        if r["last_out"] is None:
+            raise SystemExit("--dump-outputs needs at least one timed step")
+        dump_outputs(args.dump_outputs, zip(("packed", "iters", "synd"), r["last_out"]), args.seed)
 
     frames_all, info_bits = totals[0], totals[1]
     value = info_bits / wall_max / 1e6
@@ -1024,9 +1100,12 @@ def main():
                                "roofline's per-batch time" if not dvb else
                                "span = HIP events around the K launches, / K"),
                       "frame_ring": r.get("ring"),
-                      "order": "measured after the GPU variants below (same process), so the "
-                               "K steps see the GPU's steady clock; --no-variants times a "
-                               "cold GPU"}
+                      "order": ("measured after the GPU variants below (same process), so the "
+                                "K steps see the GPU's steady clock; --no-variants times a "
+                                "cold GPU" if args.full else
+                                "measured after %g ms of the timed path itself, untimed "
+                                "(--preroll-ms), so the K steps see the GPU's steady clock"
+                                % args.preroll_ms)}
 
     if pre["serial"]:
         line["serial_1_batch_in_flight"] = pre["serial"]
@@ -1034,8 +1113,8 @@ def main():
         line["variants_1gpu"] = pre["variants"]
     variant_outs = pre["outs"]
 
-    # ---- CPU baseline + parity (the oracle as checker) ----------------------
-    if not args.no_cpu_baseline:
+    # ---- CPU baseline + parity (the oracle as checker): --full ---------------
+    if args.full and not args.no_cpu_baseline:
         sys.path.insert(0, REPO)
         from oracle import oracle as orc
         threads, visible = cpu_share()

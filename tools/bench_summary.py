@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Prints the headline numbers of a bench.py JSON line (file argument)."""
+"""Prints the headline numbers of a bench.py JSON line (file argument); the
+parity, serial, variant, config 4 and block rows are those of a --full run."""
 import json
 import sys
 

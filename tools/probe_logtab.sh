@@ -8,7 +8,7 @@ set -o pipefail
 out=gpurun_out/probe_logtab
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-args="--no-cpu-baseline --no-variants --no-config4 --no-block --steps 20 --warmup 5"
+args="--no-cpu-baseline --no-variants --no-config4 --no-block --preroll-ms 0 --steps 20 --warmup 5"
 LDPC_PKG_DIR=$PWD/ab/P timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU \
   -d "$out/P" -o P --output-format csv -- python3 bench.py $args > "$out/P.log" 2>&1 &&
 timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU \

@@ -5,7 +5,7 @@
 # edge-message passes.  Output: gpurun_out/prof/dvb_{ms,edge}/...
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-args="--code dvbs2 --steps 2 --warmup 0 --inflight 1 --no-cpu-baseline"
+args="--code dvbs2 --steps 2 --warmup 0 --inflight 1 --no-cpu-baseline --preroll-ms 0"
 for v in ${DVB_VARIANTS:-ms edge}; do
   out=gpurun_out/prof/dvb_$v
   mkdir -p $out

@@ -6,7 +6,7 @@
 # Output: gpurun_out/prof/msn_<mode>/...
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-args="--code dvbs2 --steps 2 --warmup 0 --inflight 1 --no-cpu-baseline --no-variants"
+args="--code dvbs2 --steps 2 --warmup 0 --inflight 1 --no-cpu-baseline --no-variants --preroll-ms 0"
 for m in ${MSN_MODES:-2 1}; do
   out=gpurun_out/prof/msn_$m
   mkdir -p $out
