@@ -175,7 +175,8 @@ __device__ __forceinline__ void log_ratio_n_packed(const double (&T)[n],
     near[i] = ex::log_is_near1(q[i]);
     const bool unit = q[i] == 1.0;
     packed[i] = near[i] && !unit;
-    const uint64_t m = __builtin_amdgcn_ballot_w64(packed[i]);
+    // the two compares' masks, combined as scalars (LDPC_EX_LANES)
+    const uint64_t m = LDPC_EX_LANES(near[i]) & LDPC_EX_LANES(!unit);
     pos[i] = unit ? zero_at
                   : base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));

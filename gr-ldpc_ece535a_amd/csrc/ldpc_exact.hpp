@@ -51,12 +51,24 @@
 #if defined(__HIP_DEVICE_COMPILE__)
 // wave-uniform "does any lane need this": the region is skipped otherwise
 #define LDPC_EX_ANY(c) (__builtin_amdgcn_ballot_w64(c) != 0)
+// the lanes of the wave where c holds, as a scalar mask.  A conjunction or a
+// flag accumulated over slots is formed from the masks of its compares
+// (LANES(a) & LANES(b), scalar AND / OR): the ballot of a combined predicate,
+// or of a flag held per lane, is materialised as a 0 / 1 VGPR and compared
+// again (two VALU each).  Host: the value's own flag.
+#define LDPC_EX_LANES(c) __builtin_amdgcn_ballot_w64(c)
+// a second, opaque copy of such a mask, in scalar registers: a wave-uniform
+// flag tested again far from its first use is otherwise carried there as a
+// 0 / 1 VGPR and compared again
+#define LDPC_EX_SCALAR_COPY(x) asm("" : "+s"(x))
 // first statement of such a rare region: an empty volatile asm cannot be
 // speculated, so the compiler keeps the branch instead of if-converting it
 // into selects evaluated on every iteration
 #define LDPC_EX_COLD() asm volatile(";ldpc_cold")
 #else
 #define LDPC_EX_ANY(c) (c)
+#define LDPC_EX_LANES(c) ((uint64_t)(c))
+#define LDPC_EX_SCALAR_COPY(x) ((void)0)
 #define LDPC_EX_COLD() ((void)0)
 #endif
 
@@ -93,8 +105,8 @@ LDPC_HD double rcp_seed(double p) {
 #endif
 }
 
-// a / b, correctly rounded, from yk = y (1 + 2^-40), y ~ 1/b with relative
-// error < 2^-45 (so b yk lies in (1 + 2^-41, 1 + 2^-39)).
+// a / b, correctly rounded, from yk ~ (1 + 2^-40) / b with relative error
+// < 2^-45 (so b yk lies in (1 + 2^-41, 1 + 2^-39): div_n's bound).
 //  1. q0 = a yk; r = fma(-b, q0, a); q1 = fma(r, yk, q0).  q1 - a/b =
 //     (a/b - q0)(b yk - 1) + rounding: q1 is within 1/2 ulp + 2^-26 ulp of
 //     a/b (the product is below 2^-78 relative), i.e. faithful -- and
@@ -135,26 +147,53 @@ LDPC_HD double div_core(double a, double b, double yk) {
 }
 
 // q[i] = a[i] / b[i], correctly rounded, from ONE reciprocal: prefix products
-// p_i = b_0 ... b_i, y = 1 / p_{n-1} (v_rcp_f64 + one Newton step), scaled
-// once by 1 + 2^-40 (div_core's yk), then backwards 1/b_i (1 + 2^-40) ~
-// y p_{i-1}, y <- y b_i (a few ulp); each quotient then takes div_core.
+// p_i = b_0 ... b_i, y ~ (1 + 2^-40) / p_{n-1} (v_rcp_f64 + one Newton step
+// whose residual carries div_core's scale), then backwards
+// (1 + 2^-40) / b_i ~ y p_{i-1}, y <- y b_i; each quotient then takes
+// div_core.
+// The bound on b_i yk.  Let P = p_{n-1} and the seed y0 = (1 + e) / P,
+// |e| <= 2^-24 (v_rcp_f64 on gfx950 is off by up to 2^27.93 ulp,
+// profiles/round3/rcp_accuracy.txt; the host tests perturb an exact seed by
+// up to 2^22 ulp, |e| < 2^-30).  The residual is one rounding of the exact
+// 1 + 2^-40 - P y0 = 2^-40 - e: rr = (2^-40 - e)(1 + d1), and
+// y1 = RN(y0 + rr y0) = y0 (1 + rr)(1 + d2), |d1|, |d2| <= 2^-53, so
+//   P y1 = (1 + e)(1 + 2^-40 - e + d1 (2^-40 - e))(1 + d2)
+//        = 1 + 2^-40 - e^2 + e 2^-40 + (terms below 2^-52.9),
+// i.e. |P y1 - (1 + 2^-40)| < 2^-48 + 2^-64 + 2^-52.9 < 2^-47.9: the scale
+// rides in the residual at no cost in accuracy (the Newton step's e^2 is the
+// same as with 1.0 there and a separate multiplication by 1 + 2^-40, which
+// this form replaces: one f64 multiplication fewer per batch).  Each p_i is
+// a rounded product and each backward step rounds once, so b_i yk differs
+// from P y1 by at most 2n + 1 factors (1 + d), |d| <= 2^-53: with n <= 16,
+// below 2^-47.9 more.  Hence |b_i yk - (1 + 2^-40)| < 2^-46.9, far inside
+// (1 + 2^-41, 1 + 2^-39), and b_i yk > 1 as div_core's sure-pass test needs
+// (tests/test_exact_div_window.py measures the products).
 // Domain: div_core's, and every prefix product normal.
+//
+// div_recips: yk[i] ~ (1 + 2^-40) / b[i], div_core's third argument for each
+// divisor; div_n: the quotients.
 template <int n>
-LDPC_HD void div_n(const double (&a)[n], const double (&b)[n], double (&q)[n]) {
+LDPC_HD void div_recips(const double (&b)[n], double (&yk)[n]) {
   double p[n];
   p[0] = b[0];
 #pragma unroll
   for (int i = 1; i < n; ++i) p[i] = p[i - 1] * b[i];
   double y = rcp_seed(p[n - 1]);
-  y = fma_(fma_(-p[n - 1], y, 1.0), y, y);
-  y = y * (1.0 + 0x1p-40);
+  y = fma_(fma_(-p[n - 1], y, 1.0 + 0x1p-40), y, y);
 #pragma unroll
   for (int i = n - 1; i > 0; --i) {
-    const double inv = y * p[i - 1];
+    yk[i] = y * p[i - 1];
     y = y * b[i];
-    q[i] = div_core(a[i], b[i], inv);
   }
-  q[0] = div_core(a[0], b[0], y);
+  yk[0] = y;
+}
+
+template <int n>
+LDPC_HD void div_n(const double (&a)[n], const double (&b)[n], double (&q)[n]) {
+  double yk[n];
+  div_recips<n>(b, yk);
+#pragma unroll
+  for (int i = n - 1; i >= 0; --i) q[i] = div_core(a[i], b[i], yk[i]);
 }
 
 // Per-k constants of expm1 (below), as doubles, for k in [kTailLo,
@@ -225,9 +264,10 @@ constexpr ExTab make_ex_tab() {
 // mid_possible: false if the caller knows every |u| < 13.5 (k <= 19), so
 // the k = 20..56 formula need not be checked for (tanh_half_n folds that
 // test into its own rare-case test).  hx[i]: the high word of |u[i]|, or any
-// word that is above 0x3fd62e42 exactly when that one is.
+// word that is above 0x3fd62e42 exactly when that one is.  k[i]: glibc's k
+// of u[i], handed back.
 template <int n>
-LDPC_HD void expm1_n(const double (&u)[n], const uint32_t (&hx)[n], double (&t)[n],
+LDPC_HD void expm1_n(const double (&u)[n], const uint32_t (&hx)[n], double (&t)[n], int (&k)[n],
                      const ExTab *tab, bool mid_possible = true) {
   constexpr double invln2 = 1.44269504088896338700e+00;
   constexpr double Q1 = -3.33333333333331316428e-02;
@@ -236,11 +276,9 @@ LDPC_HD void expm1_n(const double (&u)[n], const uint32_t (&hx)[n], double (&t)[
   constexpr double Q4 = 4.00821782732936239552e-06;
   constexpr double Q5 = -2.01099218183624371326e-07;
   double x[n], c[n], hxs[n], num[n], den[n], q[n];
-  int k[n];
   bool edge = false;
 #pragma unroll
   for (int i = 0; i < n; ++i) {
-    const uint32_t sgn = hiw(u[i]) & 0x80000000u;
     // k = (int)(invln2 * u + (u > 0 ? 0.5 : -0.5)), truncation toward zero
     // (|k| <= 63 here).  glibc takes k = -1 for hx in (0x3fd62e42,
     // 0x3FF0A2B2) instead of this rounding, but on that range (u < 0 here)
@@ -251,7 +289,12 @@ LDPC_HD void expm1_n(const double (&u)[n], const uint32_t (&hx)[n], double (&t)[
     // (0.5 ln2, 0x3fd62e42ffffffff] -- high word 0x3fd62e42, where glibc
     // takes k = 0 and the rounding may give -1 -- needs the select, in a
     // branch a wave takes only when one of its lanes has that high word.
-    k[i] = (int)(invln2 * u[i] + from_hi(0x3fe00000u | sgn));
+    // The +-0.5 is added as 0.5 to the magnitude and u's sign put back on the
+    // sum (one bit-field insert on its high word, no constant to assemble):
+    // rounding is odd-symmetric, so with s = sign(u), RN(invln2 u) =
+    // s RN(invln2 |u|) and RN(s a + s 0.5) = s RN(a + 0.5), the same double
+    // as glibc's sum; u = -0 gives -0.5 either way (k = 0).
+    k[i] = (int)__builtin_copysign(invln2 * __builtin_fabs(u[i]) + 0.5, u[i]);
     edge |= hx[i] == 0x3fd62e42u;
   }
   if (LDPC_EX_ANY(edge)) {
@@ -316,7 +359,8 @@ LDPC_HD void expm1_n(const double (&u)[n], double (&t)[n], const ExTab *tab,
   uint32_t hx[n];
 #pragma unroll
   for (int i = 0; i < n; ++i) hx[i] = hiw(u[i]) & 0x7fffffffu;
-  expm1_n<n>(u, hx, t, tab, mid_possible);
+  int k[n];
+  expm1_n<n>(u, hx, t, k, tab, mid_possible);
 }
 
 // ---------------------------------------------------------------------------
@@ -334,7 +378,7 @@ LDPC_HD void tanh_half_n(const double (&m)[n], double (&z)[n], const ExTab *tab)
   static_assert(n <= 8, "the tanh divisors (up to 2^63 each) share one prefix product");
   double u[n], t[n], num[n], den[n], q[n];
   uint32_t hm[n];
-  bool special = false;
+  uint64_t special = 0;  // (device: lanes of the wave; host: this value's flag)
 #pragma unroll
   for (int i = 0; i < n; ++i) {
     // x = m / 2 and glibc's expm1 argument +-2|x| = +-|m| (exact: m / 2 is
@@ -351,9 +395,12 @@ LDPC_HD void tanh_half_n(const double (&m)[n], double (&z)[n], const ExTab *tab)
     // degree 1 has no other edge, so its bit message is the empty sum +0.0
     // every iteration (3 of the reference H's 64 columns), and with them in
     // the special set every wave took the special branches every iteration
-    special |= im - 0x3c900000u >= 0x402b0000u - 0x3c900000u && m[i] != 0.0;
+    special |= LDPC_EX_LANES(im - 0x3c900000u >= 0x402b0000u - 0x3c900000u) &
+               LDPC_EX_LANES(m[i] != 0.0);
   }
-  const bool any_special = LDPC_EX_ANY(special);
+  const bool any_special = special != 0;  // wave-uniform on the device
+  uint64_t special_again = special;        // for the test after the divisions
+  LDPC_EX_SCALAR_COPY(special_again);
   if (any_special) {
     LDPC_EX_COLD();
 #pragma unroll
@@ -373,10 +420,15 @@ LDPC_HD void tanh_half_n(const double (&m)[n], double (&z)[n], const ExTab *tab)
   uint32_t hx[n];
 #pragma unroll
   for (int i = 0; i < n; ++i) hx[i] = hm[i] & 0x7fffffffu;
-  expm1_n<n>(u, hx, t, tab, any_special);
+  // |x| >= 1 exactly when expm1's k > 0: u = +|m| >= 2 there (k >= 3), and
+  // u = -|m| <= 0 otherwise (k <= 0).  k is in a register until expm1's last
+  // step; testing it saves the mask of hm's exponent bit.  (A NaN lane has
+  // k = 0 whatever its bits: its z is replaced below.)
+  int k[n];
+  expm1_n<n>(u, hx, t, k, tab, any_special);
 #pragma unroll
   for (int i = 0; i < n; ++i) {
-    const bool big = (hm[i] & 0x7fffffffu) >= 0x40000000u;  // |x| >= 1
+    const bool big = k[i] > 0;
     num[i] = big ? 2.0 : -t[i];
     den[i] = t[i] + 2.0;
   }
@@ -388,12 +440,12 @@ LDPC_HD void tanh_half_n(const double (&m)[n], double (&z)[n], const ExTab *tab)
     // so both are |q + w| with w = -1 or +0 -- one constant select (its low
     // word is 0 either way) instead of a double one -- and the magnitude
     // goes in with the sign transfer
-    const bool big = (hm[i] & 0x7fffffffu) >= 0x40000000u;
+    const bool big = k[i] > 0;
     const double r = q[i] + from_hi(big ? 0xbff00000u : 0u);
     const uint32_t zh = (hiw(r) & 0x7fffffffu) | (hm[i] & 0x80000000u);
     z[i] = dbl(((uint64_t)zh << 32) | (uint32_t)bits(r));
   }
-  if (any_special) {
+  if (special_again != 0) {
     LDPC_EX_COLD();
 #pragma unroll
     for (int i = 0; i < n; ++i) {
