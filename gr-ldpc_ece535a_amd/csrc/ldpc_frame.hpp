@@ -228,10 +228,11 @@ __device__ __forceinline__ FrameResult decode_frame(const CodeView &code, const 
   if constexpr (kCols) {
     // Column-centric sum-product.  A column lane has all of its column's
     // check messages after one gather, so it computes the posterior
-    // (:519-532) and, after the exit test, every bit message of its column,
+    // (:519-532) and every bit message of its column,
     // M(j,i) = sum_{k != j} (E(k,i) + r(i)) in ascending k from +0.0
     // (:540-553) -- the same additions in the same order as the edge form --
-    // and scatters tanh(M(j,i)/2) to the edges' tb slots.  The edge lanes
+    // and, after the exit test, scatters tanh(M(j,i)/2) to the edges' tb
+    // slots.  The edge lanes
     // then only gather row neighbours.  Saves the edge form's per-edge
     // column gathers and repeated (E + r) sums.
     // a missing column entry was relocated to this lane's zero cell
@@ -427,9 +428,10 @@ __device__ __forceinline__ FrameResult decode_frame(const CodeView &code, const 
         post[q] = acc;
         hard[q] = __builtin_amdgcn_ballot_w64(acc <= Real(0)) & col_ok[q];
       }
-      // the next iteration's operands are computed before the exit test (on
-      // the last iteration they are dead stores into this wave's tb), so the
-      // syndrome's ballot / scalar chain overlaps the tanh arithmetic
+      // the leave-one-out sums come before the exit test, so the syndrome's
+      // ballot / scalar chain overlaps their additions; the tanh pass comes
+      // after it: a frame's last iteration, at the cap or on a zero syndrome,
+      // computes no operands that nothing would read
       Real mv[NW][DVN];
 #pragma unroll
       for (int q = 0; q < NW; ++q)
@@ -472,6 +474,12 @@ __device__ __forceinline__ FrameResult decode_frame(const CodeView &code, const 
         }
       }
 #endif
+      weight = syndrome();
+      used = h + 1;
+      if (h + 1 == a.max_iters) break;
+      if ((h + 1) % a.et_period == 0 && weight == 0) break;
+      // F64_FAST's `open` is read by a following iteration only: an exit
+      // above leaves it as it was
       if constexpr (PREC != 3) {
         // tanh(m/2), :509: glibc's, bit for bit; mode 0 forms the column's
         // DVN quotients from one reciprocal
@@ -520,10 +528,6 @@ __device__ __forceinline__ FrameResult decode_frame(const CodeView &code, const 
 #pragma unroll
           for (int k = 0; k < DVN; ++k) lds_st<Real>(ta[q][k], Math<PREC>::tanh_half(mv[q][k], logtab));
       }
-      weight = syndrome();
-      used = h + 1;
-      if (h + 1 == a.max_iters) break;
-      if ((h + 1) % a.et_period == 0 && weight == 0) break;
     }
   } else if constexpr (METHOD == 1 || METHOD == 0) {
     // the tables were relocated to LDS byte addresses (decode_small_kernel):
