@@ -26,6 +26,7 @@
 #include "ldpc_graph.hpp"
 #include "ldpc_kernels.hpp"
 #include "ldpc_layout.hpp"
+#include "ldpc_onchip.hpp"
 
 using ldpc::ColRec;
 using ldpc::EdgeColRec;
@@ -196,6 +197,13 @@ struct ldpc_ctx {
   void *d_work = nullptr;
   size_t work_bytes = 0;
   size_t work_limit = (size_t)8 << 30;
+  // on-chip path (ldpc_onchip.hip, LDPC_FLAG_ONCHIP): a large-code context
+  // whose min-sum / sum-product decodes run one frame per workgroup in LDS,
+  // with frame queues (d_tickets) like the small-code path's
+  bool onchip = false;
+  uint32_t *d_oc_erow = nullptr, *d_oc_ecol = nullptr, *d_oc_rows = nullptr, *d_oc_cols = nullptr;
+  uint16_t *d_oc_ci = nullptr, *d_oc_ce = nullptr;
+  int oc_resident[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};  // workgroups the device holds, per kernel
   // device encoder (built on first ldpc_encode_device): 1 small (A = H_p^-1 H_d
   // bit rows in d_encA), 2 IRA staircase, -1 no systematic encoder
   int enc_kind = 0;
@@ -537,6 +545,48 @@ int build_graph(ldpc_ctx *ctx, std::vector<int32_t> &cp, std::vector<int32_t> &c
   ctx->KB = (ctx->K + 7) / 8;
   ctx->graph = true;
   return LDPC_OK;
+}
+
+// LDPC_FLAG_ONCHIP: the code must fit the on-chip kernels for both methods at
+// every precision (ldpc_plan_onchip); decided from the shape alone, before
+// any device is looked up.
+int check_onchip(ldpc_ctx *ctx) {
+  for (int method = 0; method < 2; ++method)
+    for (int prec = 0; prec < 4; ++prec) {
+      ldpc::OnchipLayout L;
+      if (ldpc::onchip_plan(ctx->M, ctx->N, ctx->E, ctx->dc_max, ctx->dv_max, method, prec, L))
+        continue;
+      char buf[256];
+      if (L.frame > ldpc::kOnchipLdsLimit)
+        snprintf(buf, sizeof buf,
+                 "the code does not fit the on-chip kernels: a frame needs %d bytes of LDS "
+                 "(method %d, precision %d), the limit is %d (M=%d N=%d E=%d)",
+                 L.frame, method, prec, ldpc::kOnchipLdsLimit, ctx->M, ctx->N, ctx->E);
+      else
+        snprintf(buf, sizeof buf,
+                 "the code does not fit the on-chip kernels: M, N, E must be <= %d (M=%d N=%d "
+                 "E=%d; a frame needs %d bytes of LDS, the limit is %d)",
+                 ldpc::kOnchipIndexMax, ctx->M, ctx->N, ctx->E, L.frame, ldpc::kOnchipLdsLimit);
+      return set_err(ctx, LDPC_EUNSUPPORTED, buf);
+    }
+  return LDPC_OK;
+}
+
+ldpc::OnchipView onchip_view(const ldpc_ctx *ctx) {
+  ldpc::OnchipView v;
+  v.erow = ctx->d_oc_erow;
+  v.ecol = reinterpret_cast<const uint2 *>(ctx->d_oc_ecol);
+  v.rows = ctx->d_oc_rows;
+  v.cols = ctx->d_oc_cols;
+  v.ci = ctx->d_oc_ci;
+  v.ce = ctx->d_oc_ce;
+  v.M = ctx->M;
+  v.N = ctx->N;
+  v.E = ctx->E;
+  v.KB = ctx->KB;
+  v.dc_max = ctx->dc_max;
+  v.dv_max = ctx->dv_max;
+  return v;
 }
 
 ldpc::GraphView graph_view(const ldpc_ctx *ctx) {
@@ -923,13 +973,27 @@ ldpc_ctx *finish_create(ldpc_ctx *ctx, int flags, int device) {
   std::vector<uint16_t> lane_col;
   std::vector<uint8_t> col_lane;
   std::vector<int32_t> cp, ce, cr;
+  const bool onchip = (flags & LDPC_FLAG_ONCHIP) != 0;
+  if (onchip && (flags & LDPC_FLAG_GRAPH)) {
+    g_create_error = "LDPC_FLAG_ONCHIP and LDPC_FLAG_GRAPH exclude each other";
+    delete ctx;
+    return nullptr;
+  }
+  ldpc::OnchipTables oct;
   int rc = LDPC_EUNSUPPORTED;
-  if (!(flags & LDPC_FLAG_GRAPH) && !ctx->H.empty())
+  if (!(flags & (LDPC_FLAG_GRAPH | LDPC_FLAG_ONCHIP)) && !ctx->H.empty())
     rc = build_tables(ctx, erecs, crecs, cols, rowmask, lane_col, col_lane,
                       !(flags & LDPC_FLAG_PLAIN_LAYOUT));
   if (rc == LDPC_EUNSUPPORTED) {
     ctx->err.clear();
     rc = build_graph(ctx, cp, ce, cr);
+  }
+  if (rc == LDPC_OK && onchip) {
+    rc = check_onchip(ctx);
+    if (rc == LDPC_OK) {
+      ctx->onchip = true;
+      ldpc::onchip_build(ctx->M, ctx->N, ctx->rp, ctx->ci, cp, ce, oct);
+    }
   }
   if (rc != LDPC_OK) {
     g_create_error = ctx->err;
@@ -947,7 +1011,7 @@ ldpc_ctx *finish_create(ldpc_ctx *ctx, int flags, int device) {
   }
   ctx->device = device;
   {  // large-code min-sum: the narrow-chunk pipeline's tables
-    ctx->narrow = ctx->graph && ctx->M <= ldpc::kMsnMaxRows;
+    ctx->narrow = ctx->graph && !ctx->onchip && ctx->M <= ldpc::kMsnMaxRows;
     if (ctx->narrow) {
       try {
         ldpc::msn_build(ctx->M, ctx->N, ctx->rp, ctx->ci, ctx->msn);
@@ -974,6 +1038,16 @@ ldpc_ctx *finish_create(ldpc_ctx *ctx, int flags, int device) {
       for (int i = 0; i < 4; ++i) upload(ctx, &ctx->d_msn[i], *t[i], "upload(storage order)", what, e);
       upload(ctx, &ctx->d_msnd[0], ctx->msn.rdesc, "upload(edge descriptors)", what, e);
       upload(ctx, &ctx->d_msnd[1], ctx->msn.cdesc, "upload(edge descriptors)", what, e);
+    }
+    if (ctx->onchip) {
+      upload(ctx, &ctx->d_oc_erow, oct.erow, "upload(on-chip rows of edges)", what, e);
+      upload(ctx, &ctx->d_oc_ecol, oct.ecol, "upload(on-chip columns of edges)", what, e);
+      upload(ctx, &ctx->d_oc_rows, oct.rows, "upload(on-chip rows)", what, e);
+      upload(ctx, &ctx->d_oc_cols, oct.cols, "upload(on-chip columns)", what, e);
+      upload(ctx, &ctx->d_oc_ci, oct.ci, "upload(on-chip col_idx)", what, e);
+      upload(ctx, &ctx->d_oc_ce, oct.ce, "upload(on-chip col_edges)", what, e);
+      std::vector<uint32_t> zeros((size_t)LDPC_TICKET_SLOTS * LDPC_TICKET_STRIDE, 0);
+      upload(ctx, &ctx->d_tickets, zeros, "upload(tickets)", what, e);
     }
   } else {
     upload(ctx, &ctx->d_erow, erecs, "upload(erow)", what, e);
@@ -1073,6 +1147,10 @@ void ldpc_destroy(ldpc_ctx *ctx) {
   if (ctx->d_srv_ctl) (void)hipFree(ctx->d_srv_ctl);
   if (ctx->d_srv_keys) (void)hipFree(ctx->d_srv_keys);
   if (ctx->d_tickets) (void)hipFree(ctx->d_tickets);
+  for (uint32_t *p : {ctx->d_oc_erow, ctx->d_oc_ecol, ctx->d_oc_rows, ctx->d_oc_cols})
+    if (p) (void)hipFree(p);
+  for (uint16_t *p : {ctx->d_oc_ci, ctx->d_oc_ce})
+    if (p) (void)hipFree(p);
   for (int32_t *p : {ctx->d_rp, ctx->d_ci, ctx->d_cp, ctx->d_ce, ctx->d_cr})
     if (p) (void)hipFree(p);
   for (int32_t *p : ctx->d_msn)
@@ -1123,7 +1201,7 @@ int ldpc_ctx_csr(const ldpc_ctx *ctx, int32_t *row_ptr_out, int32_t *col_idx_out
 
 int ldpc_ctx_path(const ldpc_ctx *ctx) {
   if (!ctx) return LDPC_EINVAL;
-  return ctx->graph ? 1 : 0;
+  return ctx->onchip ? 2 : ctx->graph ? 1 : 0;
 }
 
 int ldpc_ctx_pipeline(const ldpc_ctx *ctx, int *frames_per_chunk, int *chunks) {
@@ -1186,6 +1264,22 @@ int ldpc_plan_layout(const uint8_t *H, int M, int N, int flags, int32_t *cell_ou
     for (int i = 0; i < N; ++i) pos_out_opt[i] = col_lane[i];
   if (model_out_opt) std::copy(tmp.layout_model, tmp.layout_model + 5, model_out_opt);
   return tmp.E;
+}
+
+int ldpc_plan_onchip(int M, int N, int E, int dc_max, int dv_max, int method, int precision,
+                     int64_t *lds_bytes_out_opt, int *threads_out_opt) {
+  g_create_error.clear();
+  if (M <= 0 || N <= 0 || M >= N || E <= 0 || dc_max < 1 || dv_max < 1)
+    return set_err(nullptr, LDPC_EINVAL, "M, N (M < N), E and the degrees must be positive");
+  if (method != LDPC_METHOD_LOGDOMAIN && method != LDPC_METHOD_SUMPRODUCT)
+    return set_err(nullptr, LDPC_EINVAL, "the on-chip kernels take min-sum and sum-product");
+  if (precision < 0 || precision > 3)
+    return set_err(nullptr, LDPC_EINVAL, "precision must be one of LDPC_PREC_*");
+  ldpc::OnchipLayout L;
+  const bool fits = ldpc::onchip_plan(M, N, E, dc_max, dv_max, method, precision, L);
+  if (lds_bytes_out_opt) *lds_bytes_out_opt = fits ? L.total : L.frame;
+  if (threads_out_opt) *threads_out_opt = L.threads;
+  return fits ? 1 : 0;
 }
 
 int ldpc_encode_device(ldpc_ctx *ctx, const uint8_t *d_data_bits, int B, uint8_t *d_codewords,
@@ -1277,7 +1371,9 @@ int decode_device_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, 
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
   void *st = hip_stream ? hip_stream : (void *)ctx->stream;
-  if (ctx->graph) {
+  // on-chip contexts: min-sum / sum-product in LDS, the rest as a large code
+  const bool onchip = ctx->onchip && (method == 0 || method == 1);
+  if (ctx->graph && !onchip) {
     if (d_win) return set_err(ctx, LDPC_EUNSUPPORTED, "window lists: small-code kernels only");
     // one workspace per context: order this decode after the previous one
     // when it was enqueued on another stream
@@ -1336,8 +1432,12 @@ int decode_device_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, 
   a.static_stride = max_iters <= 10 ? 1 : 0;
   a.fair_cycles = ctx->fair_cycles;
   uint32_t advance = 0;
-  rc = ldpc::launch_decode(code_view(ctx), a, method, precision, ctx->slots, ctx->nw,
-                           ctx->waves_per_cu, ctx->schedule, st, &advance);
+  if (onchip)
+    rc = ldpc::launch_onchip_decode(onchip_view(ctx), a, method, precision, st, ctx->oc_resident,
+                                    &advance);
+  else
+    rc = ldpc::launch_decode(code_view(ctx), a, method, precision, ctx->slots, ctx->nw,
+                             ctx->waves_per_cu, ctx->schedule, st, &advance);
   if (rc == -2) return set_err(ctx, LDPC_EUNSUPPORTED, "no kernel for this code shape");
   if (rc != 0) return hip_err(ctx, hipGetLastError(), "kernel launch");
   ctx->queues[q].base += advance;  // what the launch adds to its counter (B with one frame per claim)
@@ -1523,9 +1623,11 @@ int decode_windows_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period,
     if (win[b] < 0 || (win[b] >> 1) + N > S)
       return set_err(ctx, LDPC_EINVAL, "window outside the input span");
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  // the on-chip kernels read each window in place, like the small-code ones
+  const bool gather = ctx->graph && !(ctx->onchip && (method == 0 || method == 1));
   const size_t b_span = al((size_t)S * 4), b_win = al((size_t)B * 8),
                // gathered frames: only the large-code kernels need them
-               b_fr = ctx->graph ? al((size_t)B * N * 4) : 0, b_pk = al((size_t)B * ctx->KB),
+               b_fr = gather ? al((size_t)B * N * 4) : 0, b_pk = al((size_t)B * ctx->KB),
                b_sy = al((size_t)B * 4);
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
@@ -1590,7 +1692,7 @@ int decode_windows_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period,
                                  ctx->stream)) != hipSuccess) {
     return hip_err(ctx, e, "hipMemcpyAsync(windows)");
   }
-  if (ctx->graph) {  // the large-code kernels read frames at a fixed stride: gather first
+  if (gather) {  // the large-code kernels read frames at a fixed stride: gather first
     if (ldpc::launch_gather_windows(d_span, d_win, B, N, d_fr, ctx->stream) != 0)
       return set_err(ctx, LDPC_EDEVICE, "gather_windows launch failed");
     rc = decode_device_impl(ctx, method, max_iters, et_period, precision, d_fr, N, 1, 1.0f, B,
@@ -1708,6 +1810,10 @@ int serve_reset_epochs(ldpc_ctx *ctx) {
 int serve_begin_impl(ldpc_ctx *ctx, int method, int max_iters, int precision, int max_windows) {
   int rc = check_decode_args(ctx, method, max_iters, 1, precision, 1, 1, ctx ? ctx->N : 1);
   if (rc != LDPC_OK) return rc;
+  if (ctx->onchip)
+    return set_err(ctx, LDPC_EUNSUPPORTED,
+                   "the window server does not run on an on-chip context (small-code kernels "
+                   "only); use ldpc_decode_windows");
   if (ctx->graph || ctx->KB > 4 || (method != 0 && method != 1))
     return set_err(ctx, LDPC_EUNSUPPORTED,
                    "the window server takes min-sum / sum-product on small codes with KB <= 4");
@@ -2076,6 +2182,10 @@ int ldpc_ring_begin(ldpc_ctx *ctx, int method, int max_iters, int et_period, int
   int rc = check_decode_args(ctx, method, max_iters, et_period, precision, 1, 1, ctx->N);
   if (rc != LDPC_OK) return rc;
   if (ctx->ring_on) return set_err(ctx, LDPC_EINVAL, "a frame ring session is open (ldpc_ring_end)");
+  if (ctx->onchip)
+    return set_err(ctx, LDPC_EUNSUPPORTED,
+                   "the frame ring does not run on an on-chip context (small-code kernels only); "
+                   "use ldpc_decode_device");
   if (ctx->graph || (method != 0 && method != 1))
     return set_err(ctx, LDPC_EUNSUPPORTED,
                    "the frame ring takes min-sum / sum-product on small codes");

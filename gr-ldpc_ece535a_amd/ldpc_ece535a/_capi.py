@@ -19,9 +19,10 @@ PREC_F64, PREC_F32, PREC_F64_LIBM, PREC_F64_FAST = 0, 1, 2, 3
 FLAG_NO_REORDER = 1
 FLAG_GRAPH = 2
 FLAG_PLAIN_LAYOUT = 4
+FLAG_ONCHIP = 8
 TEST_SERVE_UNCHECKED, TEST_SERVE_EPOCH, TEST_SERVE_EPOCH_NOW, TEST_STREAM_OVERLAP = 1, 2, 3, 4
 SERVE_EPOCH_LIMIT = (1 << 23) - (1 << 16)
-PATH_SMALL, PATH_GRAPH = 0, 1
+PATH_SMALL, PATH_GRAPH, PATH_ONCHIP = 0, 1, 2
 MODE_LATENCY, MODE_THROUGHPUT = 0, 1
 ERRORS = {0: "LDPC_OK", -1: "LDPC_EINVAL", -2: "LDPC_EUNSUPPORTED", -3: "LDPC_EDEVICE",
           -4: "LDPC_ESINGULAR", -5: "LDPC_ENOMEM", -6: "LDPC_ETIMEOUT"}
@@ -49,6 +50,7 @@ SIGNATURES = {
     "ldpc_ctx_layout": (_i, [_vp, _i32p]),
     "ldpc_plan_layout": (_i, [_u8p, _i, _i, _i, _i32p, _i32p, _i32p]),
     "ldpc_plan_storage_order": (_i, [_i, _i, _i32p, _i32p, _i32p, _i32p, _i64p]),
+    "ldpc_plan_onchip": (_i, [_i, _i, _i, _i, _i, _i, _i, _i64p, _i32p]),
     "ldpc_set_work_limit": (_i, [_vp, _i64]),
     "ldpc_encode_device": (_i, [_vp, _vp, _i, _vp, _vp]),
     "ldpc_random_bits": (_i, [_vp, _i64, ctypes.c_uint64, _vp]),
@@ -192,6 +194,18 @@ def plan_storage_order(csr):
     return dict(order=order, rpos=rpos, cpos=cpos, score=(int(score[0]), int(score[1])))
 
 
+def plan_onchip(M, N, E, dc_max, dv_max, method=METHOD_SUMPRODUCT, precision=PREC_F64):
+    """ldpc_plan_onchip (host only, no GPU): dict with fits (the on-chip
+    kernels take a code of this shape for this method and precision),
+    lds_bytes (LDS its workgroup declares: the frame's state, plus the code's
+    tables where they fit behind it) and threads (of the workgroup)."""
+    lds, threads = ctypes.c_int64(0), ctypes.c_int32(0)
+    fits = _check(lib().ldpc_plan_onchip(int(M), int(N), int(E), int(dc_max), int(dv_max),
+                                         int(method), int(precision), ctypes.byref(lds),
+                                         ctypes.byref(threads)))
+    return dict(fits=bool(fits), lds_bytes=lds.value, threads=threads.value)
+
+
 class Decoder:
     """One decode context (device tables + stream) for one H.
 
@@ -199,12 +213,15 @@ class Decoder:
     or csr=(M, N, row_ptr, col_idx) for a sparse H used as given.
     force_graph=True selects the large-code (HBM message) kernels even for a
     code the small-code kernel could take; plain_layout=True keeps the
-    small-code kernel's edges and columns in CSR order (A/B and tests)."""
+    small-code kernel's edges and columns in CSR order (A/B and tests);
+    onchip=True runs min-sum / sum-product on the on-chip kernels (one frame
+    per workgroup, messages in LDS; path == PATH_ONCHIP) for any code that
+    fits them (plan_onchip), and raises for one that does not."""
 
     def __init__(self, H=None, reorder=True, device=0, csr=None, force_graph=False,
-                 plain_layout=False):
+                 plain_layout=False, onchip=False):
         flags = ((0 if reorder else FLAG_NO_REORDER) | (FLAG_GRAPH if force_graph else 0) |
-                 (FLAG_PLAIN_LAYOUT if plain_layout else 0))
+                 (FLAG_PLAIN_LAYOUT if plain_layout else 0) | (FLAG_ONCHIP if onchip else 0))
         if csr is not None:
             M, N, rp, ci = csr
             rp = np.ascontiguousarray(rp, np.int32)

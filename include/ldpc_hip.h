@@ -79,6 +79,11 @@ extern "C" {
 #define LDPC_FLAG_GRAPH 2      /* force the large-code (HBM message) kernels */
 #define LDPC_FLAG_PLAIN_LAYOUT 4 /* small codes: edges / columns in CSR order (no
                                     LDS bank-conflict layout search; A/B only) */
+#define LDPC_FLAG_ONCHIP 8     /* min-sum / sum-product on the on-chip kernels (one
+                                  frame per workgroup, messages in LDS) for any
+                                  code that fits them (ldpc_plan_onchip), small
+                                  ones included; LDPC_EUNSUPPORTED otherwise,
+                                  LDPC_EINVAL together with LDPC_FLAG_GRAPH */
 
 /* error codes */
 #define LDPC_OK 0
@@ -144,6 +149,20 @@ int ldpc_plan_layout(const uint8_t *H, int M, int N, int flags, int32_t *cell_ou
 int ldpc_plan_storage_order(int M, int N, const int32_t *row_ptr, const int32_t *col_idx,
                             int32_t *rpos_out_opt, int32_t *cpos_out_opt, int64_t *score_out_opt);
 
+/* The on-chip path's plan for a code of M x N with E ones and largest check /
+ * variable degrees dc_max / dv_max, decoded with `method` (LDPC_METHOD_LOGDOMAIN
+ * or LDPC_METHOD_SUMPRODUCT) at `precision` (no GPU): the bytes of LDS a
+ * workgroup declares -- one frame's state (two message arrays of E reals, the
+ * mode's log table, N channel floats, N decision bytes) plus, where they fit
+ * behind it, copies of the code's tables -- and the threads of the workgroup (a
+ * multiple of 64, at most 1024).  Returns 1 when the code fits (degrees <= 32 /
+ * 16, M, N, E <= 65535, a frame's state within 163840 bytes), 0 when it does
+ * not (lds_bytes is then the frame's state alone), or a negative code for bad
+ * arguments.  ldpc_create* with LDPC_FLAG_ONCHIP accept a code when this
+ * returns 1 for both methods at every precision. */
+int ldpc_plan_onchip(int M, int N, int E, int dc_max, int dv_max, int method, int precision,
+                     int64_t *lds_bytes_out_opt, int *threads_out_opt);
+
 /* ---- device context ----------------------------------------------- */
 
 /* Builds the decoder's view of H (reorderHMatrix unless
@@ -172,7 +191,9 @@ int ldpc_ctx_h(const ldpc_ctx *ctx, uint8_t *H_out);
 /* Copies the context's H as CSR (row_ptr: M+1, col_idx: E); either may be NULL. */
 int ldpc_ctx_csr(const ldpc_ctx *ctx, int32_t *row_ptr_out, int32_t *col_idx_out);
 /* 0: small-code kernel (frame per wave / workgroup, registers + LDS);
- * 1: large-code kernels (messages in HBM). */
+ * 1: large-code kernels (messages in HBM);
+ * 2: on-chip kernels (LDPC_FLAG_ONCHIP: frame per workgroup, messages in LDS;
+ *    bit-flip and hard decision run on the large-code kernels). */
 int ldpc_ctx_path(const ldpc_ctx *ctx);
 /* The large-code min-sum pipeline's configuration: 1 and the
  * frames per chunk and the chunks in flight (LDPC_MSN_CHUNKS, else the
