@@ -194,7 +194,14 @@ __device__ __forceinline__ FrameResult decode_frame(const CodeView &code, const 
 #pragma unroll
   for (int q = 0; q < NW; ++q) {
     const int c = lane + 64 * q;
-    rb[c] = -(Real)xin[q];
+    // the negation is an operation of its own, as in the reference: folded
+    // into the constant of a later multiply (tanh's m * 0.5, which the
+    // column-centric form applies to this lane's own r), a NaN sample would
+    // keep the sign that negating tx flips, and the posteriors it reaches
+    // would differ in their sign bit
+    Real r = -(Real)xin[q];
+    asm volatile("" : "+v"(r));
+    rb[c] = r;
     post[q] = (Real)xin[q];
   }
 

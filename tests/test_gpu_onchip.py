@@ -11,20 +11,11 @@ entry points the path hands on or refuses."""
 import numpy as np
 import pytest
 
+from shape_cases import degree_limit_code as _degree_limit_code, same_bits as _same_bits
+
 pytestmark = pytest.mark.gpu
 
 KEYS = ("bits", "packed", "iters", "synd")
-
-
-def _same_bits(a, b, what=""):
-    """Posteriors as uint32 patterns: signed zeros and the sign and payload
-    of NaNs count."""
-    a = np.ascontiguousarray(a, np.float32).view(np.uint32)
-    b = np.ascontiguousarray(b, np.float32).view(np.uint32)
-    bad = a != b
-    assert not bad.any(), ("%s: %d of %d posteriors differ, first at %s: %s vs %s" % (
-        what, bad.sum(), bad.size, np.argwhere(bad)[0], [hex(v) for v in a[bad][:4]],
-        [hex(v) for v in b[bad][:4]]))
 
 
 def _eq(out, ref, keys=KEYS, what=""):
@@ -180,27 +171,6 @@ def test_n2160_vs_oracle(c2160, method, db):
 
 
 # ---- 4. the kernels' degree limits ---------------------------------------------
-
-def _degree_limit_code():
-    """M = 40, N = 120: a staircase (row 0 and column 38 of degree 1) plus
-    random weight-3 columns, one column of degree 16 and one row filled up to
-    degree 32."""
-    M, N = 40, 120
-    rng = np.random.Generator(np.random.PCG64(40))
-    H = np.zeros((M, N), np.uint8)
-    j = np.arange(M)
-    H[j, j] = 1
-    H[j[1:-1], j[1:-1] - 1] = 1      # row 39 keeps only its own column: column 38 has degree 1
-    H[1:17, 40] = 1
-    for c in range(41, N):
-        H[rng.choice(np.arange(1, M), 3, replace=False), c] = 1
-    free = [c for c in range(41, N) if not H[20, c]]
-    for c in free[:32 - int(H[20].sum())]:
-        H[20, c] = 1
-    from oracle import oracle as orc
-    rp, ci = orc.dense_to_csr(H)
-    return (M, N, rp, ci), H
-
 
 @pytest.mark.parametrize("method", [0, 1])
 def test_degree_limits(method):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import ldpc_ece535a as L
+from shape_cases import CASES, SMALL
 
 
 def kernel_shape(M, N, E, dc, dv):
@@ -121,14 +122,17 @@ def codes(golden):
     out += [(n, ref[n]) for n in ("hData1", "hData2", "hData3", "hData4", "hData5")]
     rng = np.random.default_rng(7)
     out += [("rand96x192", random_code(rng, 96, 192, 2)), ("rand64x128", random_code(rng, 64, 128, 3))]
+    out = [(n, H, True) for n, H in out]
+    # every small-code dispatch cell (tests/shape_cases.py), H used as given
+    out += [(n, np.array(CASES[n].H), False) for n in SMALL]
     return out
 
 
 def test_layout_is_a_placement_and_never_worse(golden):
-    for name, H in codes(golden):
-        Hr, _ = L.reorder_h(H)
+    for name, H, reorder in codes(golden):
+        Hr = L.reorder_h(H)[0] if reorder else H
         M, N = Hr.shape
-        lay = L.plan_layout(H)
+        lay = L.plan_layout(H, reorder=reorder)
         cell, pos, m = lay["cell"], lay["pos"], lay["model"]
         E = int(Hr.sum())
         S = (E + 63) // 64
@@ -137,7 +141,7 @@ def test_layout_is_a_placement_and_never_worse(golden):
         assert cell.min() >= 0 and cell.max() < 64 * S, name
         assert sorted(pos.tolist()) == list(range(N)), name  # positions 0..N-1: the columns
         assert m["cc"] + m["ec"] <= m["plain_cc"] + m["plain_ec"], (name, m)
-        plain = L.plan_layout(H, plain=True)
+        plain = L.plan_layout(H, reorder=reorder, plain=True)
         assert (plain["cell"] == np.arange(E)).all() and (plain["pos"] == np.arange(N)).all()
         assert plain["model"]["searched"] == 0
         assert NW * 64 >= N
@@ -150,15 +154,16 @@ def test_default_h_layout_is_conflict_free(golden):
     assert m["plain_cc"] > 40 and m["plain_ec"] > 20, m  # the CSR layout it replaces
 
 
-@pytest.mark.parametrize("name", ["default", "hData4", "hData5", "hData2", "rand64x128"])
+@pytest.mark.parametrize("name", ["default", "hData4", "hData5", "hData2", "rand64x128",
+                                  "b_48x64", "c_32x64", "g_250x256"])
 def test_model_matches_independent_restatement(golden, name):
-    H = dict(codes(golden))[name]
-    Hr, _ = L.reorder_h(H)
+    H, reorder = {n: (H, r) for n, H, r in codes(golden)}[name]
+    Hr = L.reorder_h(H)[0] if reorder else H
     M, N = Hr.shape
     E = int(Hr.sum())
     cols = kernel_shape(M, N, E, Hr.sum(1).max(), Hr.sum(0).max())[4]
     for plain in (False, True):
-        lay = L.plan_layout(H, plain=plain)
+        lay = L.plan_layout(H, reorder=reorder, plain=plain)
         m = lay["model"]
         ec = model(Hr, lay["cell"], lay["pos"], False)
         key = "plain_" if plain or not m["searched"] else ""
