@@ -26,6 +26,7 @@
 #include "ldpc_graph.hpp"
 #include "ldpc_kernels.hpp"
 #include "ldpc_layout.hpp"
+#include "ldpc_layered.hpp"
 #include "ldpc_onchip.hpp"
 
 using ldpc::ColRec;
@@ -204,6 +205,17 @@ struct ldpc_ctx {
   uint32_t *d_oc_erow = nullptr, *d_oc_ecol = nullptr, *d_oc_rows = nullptr, *d_oc_cols = nullptr;
   uint16_t *d_oc_ci = nullptr, *d_oc_ce = nullptr;
   int oc_resident[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};  // workgroups the device holds, per kernel
+  // layered min-sum (ldpc_layered.hip, ldpc_decode_layered*), on any context
+  // whose code fits: the plan in force (made on first use, or the caller's),
+  // and the tables built and uploaded from it by the first decode after it
+  // changed
+  std::vector<int32_t> lay_of_row;
+  int lay_L = 0;            // 0: no plan yet
+  bool lay_ready = false;   // the device tables are those of lay_of_row
+  ldpc::LayeredLayout lay_f64{}, lay_f32{};
+  uint32_t *d_lay_rows = nullptr, *d_lay_off = nullptr;
+  uint16_t *d_lay_ci = nullptr, *d_lay_order = nullptr;
+  int lay_resident[2] = {0, 0};  // workgroups the device holds, f64 / f32 kernel
   // device encoder (built on first ldpc_encode_device): 1 small (A = H_p^-1 H_d
   // bit rows in d_encA), 2 IRA staircase, -1 no systematic encoder
   int enc_kind = 0;
@@ -1149,7 +1161,9 @@ void ldpc_destroy(ldpc_ctx *ctx) {
   if (ctx->d_tickets) (void)hipFree(ctx->d_tickets);
   for (uint32_t *p : {ctx->d_oc_erow, ctx->d_oc_ecol, ctx->d_oc_rows, ctx->d_oc_cols})
     if (p) (void)hipFree(p);
-  for (uint16_t *p : {ctx->d_oc_ci, ctx->d_oc_ce})
+  for (uint16_t *p : {ctx->d_oc_ci, ctx->d_oc_ce, ctx->d_lay_ci, ctx->d_lay_order})
+    if (p) (void)hipFree(p);
+  for (uint32_t *p : {ctx->d_lay_rows, ctx->d_lay_off})
     if (p) (void)hipFree(p);
   for (int32_t *p : {ctx->d_rp, ctx->d_ci, ctx->d_cp, ctx->d_ce, ctx->d_cr})
     if (p) (void)hipFree(p);
@@ -1338,6 +1352,32 @@ int ldpc_set_work_limit(ldpc_ctx *ctx, int64_t bytes) {
 
 namespace {
 
+// The frame-queue counter of stream `st` on this context (ldpc_kernels.hpp
+// DecodeArgs::ticket): q is its slot in ctx->queues / ctx->d_tickets.
+int stream_queue(ldpc_ctx *ctx, void *st, size_t &q) {
+  hipError_t e;
+  q = 0;
+  while (q < ctx->queues.size() && ctx->queues[q].stream != st) ++q;
+  if (q == ctx->queues.size()) {
+    if (q == LDPC_TICKET_SLOTS) {
+      // more streams than counters: drain the device, start every queue over.
+      // The memset runs on the null stream, which non-blocking streams are
+      // not ordered after: wait for it before any stream launches again.
+      if ((e = hipDeviceSynchronize()) != hipSuccess ||
+          (e = hipMemset(ctx->d_tickets, 0,
+                         (size_t)LDPC_TICKET_SLOTS * LDPC_TICKET_STRIDE * sizeof(uint32_t))) !=
+              hipSuccess ||
+          (e = hipDeviceSynchronize()) != hipSuccess)
+        return hip_err(ctx, e, "ticket reset");
+      ctx->queues.clear();
+      q = 0;
+    }
+    // slots are handed out in order from zeroed memory (creation, reset)
+    ctx->queues.push_back({st, 0u});
+  }
+  return LDPC_OK;
+}
+
 // Enqueues one decode of device-resident frames.  pm_half > 0: B = 2 pm_half
 // and frames pm_half.. re-decode windows 0..pm_half-1 with -polarity
 // (DecodeArgs::pm_half), in the same launch on the small-code path.
@@ -1404,26 +1444,8 @@ int decode_device_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, 
     return LDPC_OK;
   }
   a.pm_half = pm_half;
-  // the stream's own frame-queue counter (ldpc_kernels.hpp DecodeArgs::ticket)
   size_t q = 0;
-  while (q < ctx->queues.size() && ctx->queues[q].stream != st) ++q;
-  if (q == ctx->queues.size()) {
-    if (q == LDPC_TICKET_SLOTS) {
-      // more streams than counters: drain the device, start every queue over.
-      // The memset runs on the null stream, which non-blocking streams are
-      // not ordered after: wait for it before any stream launches again.
-      if ((e = hipDeviceSynchronize()) != hipSuccess ||
-          (e = hipMemset(ctx->d_tickets, 0,
-                         (size_t)LDPC_TICKET_SLOTS * LDPC_TICKET_STRIDE * sizeof(uint32_t))) !=
-              hipSuccess ||
-          (e = hipDeviceSynchronize()) != hipSuccess)
-        return hip_err(ctx, e, "ticket reset");
-      ctx->queues.clear();
-      q = 0;
-    }
-    // slots are handed out in order from zeroed memory (creation, reset)
-    ctx->queues.push_back({st, 0u});
-  }
+  if ((rc = stream_queue(ctx, st, q)) != LDPC_OK) return rc;
   a.ticket = ctx->d_tickets + q * LDPC_TICKET_STRIDE;
   a.ticket_base = ctx->queues[q].base;
   a.waves = 0;
@@ -1444,18 +1466,171 @@ int decode_device_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, 
   return LDPC_OK;
 }
 
+// ---- layered min-sum (ldpc_layered.hip) ------------------------------------
+
+int largest_layer(const std::vector<int32_t> &layer_of_row, int L) {
+  std::vector<int> n((size_t)L, 0);
+  int most = 0;
+  for (int32_t l : layer_of_row) most = std::max(most, ++n[l]);
+  return most;
+}
+
+// The context's plan: the planner's unless the caller has set one.  Host only.
+void ensure_layer_plan(ldpc_ctx *ctx) {
+  if (ctx->lay_L > 0) return;
+  ctx->lay_L = ldpc::plan_layers(ctx->M, ctx->N, ctx->rp.data(), ctx->ci.data(), ctx->lay_of_row);
+  ctx->lay_ready = false;
+}
+
+// Builds and uploads the layered decoder's tables from the context's CSR and
+// the plan in force (first use, or the first decode after ldpc_set_layers).
+int prepare_layered(ldpc_ctx *ctx) {
+  ensure_layer_plan(ctx);
+  if (ctx->lay_ready) return LDPC_OK;
+  const int most = largest_layer(ctx->lay_of_row, ctx->lay_L);
+  ldpc::layered_layout(ctx->M, ctx->N, ctx->E, ctx->dc_max, ctx->lay_L, most, 0, ctx->lay_f64);
+  const bool f32 = ldpc::layered_layout(ctx->M, ctx->N, ctx->E, ctx->dc_max, ctx->lay_L, most, 1,
+                                        ctx->lay_f32);
+  if (!f32) {  // what no precision fits; a code that fits float alone is refused per decode
+    char buf[256];
+    snprintf(buf, sizeof buf,
+             "the code does not fit the layered kernels: a frame needs %d bytes of LDS in float "
+             "(%d in double), the limit is %d; M, N, E must be <= %d and check degrees <= %d "
+             "(M=%d N=%d E=%d dc_max=%d)",
+             ctx->lay_f32.frame, ctx->lay_f64.frame, ldpc::kLayeredLdsLimit,
+             ldpc::kLayeredIndexMax, ldpc::kLayeredDcMax, ctx->M, ctx->N, ctx->E, ctx->dc_max);
+    return set_err(ctx, LDPC_EUNSUPPORTED, buf);
+  }
+  ldpc::LayeredTables t;
+  ldpc::layered_build(ctx->M, ctx->rp.data(), ctx->ci.data(), ctx->lay_of_row, ctx->lay_L, t);
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
+  // decodes that read the previous plan's tables may still run (any stream)
+  if (ctx->d_lay_rows && (e = hipDeviceSynchronize()) != hipSuccess)
+    return hip_err(ctx, e, "hipDeviceSynchronize");
+  for (uint32_t **p : {&ctx->d_lay_rows, &ctx->d_lay_off})
+    if (*p) {
+      (void)hipFree(*p);
+      *p = nullptr;
+    }
+  for (uint16_t **p : {&ctx->d_lay_ci, &ctx->d_lay_order})
+    if (*p) {
+      (void)hipFree(*p);
+      *p = nullptr;
+    }
+  const char *what = nullptr;
+  upload(ctx, &ctx->d_lay_rows, t.rows, "upload(layered rows)", what, e);
+  upload(ctx, &ctx->d_lay_ci, t.ci, "upload(layered col_idx)", what, e);
+  upload(ctx, &ctx->d_lay_order, t.order, "upload(layered row order)", what, e);
+  upload(ctx, &ctx->d_lay_off, t.off, "upload(layer offsets)", what, e);
+  if (!what && !ctx->d_tickets) {  // large-code contexts have no frame queues of their own
+    std::vector<uint32_t> zeros((size_t)LDPC_TICKET_SLOTS * LDPC_TICKET_STRIDE, 0);
+    upload(ctx, &ctx->d_tickets, zeros, "upload(tickets)", what, e);
+  }
+  if (what) return hip_err(ctx, e, what);
+  ctx->lay_resident[0] = ctx->lay_resident[1] = 0;  // the layout's threads and bytes may differ
+  ctx->lay_ready = true;
+  return LDPC_OK;
+}
+
+// What a layered decode needs beyond check_decode_args, in the order the
+// refusals are documented: no ring session, a scale in (0, 1], tables for the
+// plan in force, and a frame that fits at this precision.  The host entry
+// point calls it before it stages anything, the device one before it launches.
+int layered_ready(ldpc_ctx *ctx, double scale, int precision) {
+  if (ctx->ring_on)
+    return set_err(ctx, LDPC_EINVAL, "a frame ring session is open (ldpc_ring_end)");
+  if (!(scale > 0.0 && scale <= 1.0))
+    return set_err(ctx, LDPC_EINVAL, "scale must be finite, in (0, 1]");
+  const int rc = prepare_layered(ctx);
+  if (rc != LDPC_OK) return rc;
+  const ldpc::LayeredLayout &lay = precision == LDPC_PREC_F32 ? ctx->lay_f32 : ctx->lay_f64;
+  if (lay.frame > ldpc::kLayeredLdsLimit) {
+    char buf[200];
+    snprintf(buf, sizeof buf,
+             "the code does not fit the layered kernels at this precision: a frame needs %d "
+             "bytes of LDS, the limit is %d (M=%d N=%d E=%d)",
+             lay.frame, ldpc::kLayeredLdsLimit, ctx->M, ctx->N, ctx->E);
+    return set_err(ctx, LDPC_EUNSUPPORTED, buf);
+  }
+  return LDPC_OK;
+}
+
+// Enqueues one layered decode of device-resident frames (decode_device_impl
+// for the layered kernel: same inputs, outputs and frame queues).
+int layered_device_impl(ldpc_ctx *ctx, double scale, int max_iters, int et_period, int precision,
+                        const float *d_in, int64_t cw_stride, int elem_stride, float polarity,
+                        int B, uint8_t *d_out_packed, uint8_t *d_out_bits_opt,
+                        int32_t *d_iters_used_opt, int32_t *d_syn_weight_opt,
+                        float *d_llr_out_opt, void *hip_stream) {
+  serve_stop(ctx);
+  int method = LDPC_METHOD_LOGDOMAIN;
+  int rc = check_decode_args(ctx, method, max_iters, et_period, precision, B, elem_stride,
+                             cw_stride);
+  if (rc != LDPC_OK) return rc;
+  if ((rc = layered_ready(ctx, scale, precision)) != LDPC_OK) return rc;
+  const int f32 = precision == LDPC_PREC_F32 ? 1 : 0;
+  const ldpc::LayeredLayout &lay = f32 ? ctx->lay_f32 : ctx->lay_f64;
+  if (B == 0) return LDPC_OK;
+  if (!d_in || !d_out_packed) return set_err(ctx, LDPC_EINVAL, "null device buffer");
+  ldpc::DecodeArgs a{};
+  a.in = d_in;
+  a.cw_stride = cw_stride;
+  a.elem_stride = elem_stride;
+  a.polarity = polarity;
+  a.B = B;
+  a.pm_half = 0;
+  a.win = nullptr;
+  a.max_iters = max_iters;
+  a.et_period = et_period;
+  a.packed = d_out_packed;
+  a.bits = d_out_bits_opt;
+  a.iters = d_iters_used_opt;
+  a.synd = d_syn_weight_opt;
+  a.llr = d_llr_out_opt;
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
+  void *st = hip_stream ? hip_stream : (void *)ctx->stream;
+  size_t q = 0;
+  if ((rc = stream_queue(ctx, st, q)) != LDPC_OK) return rc;
+  a.ticket = ctx->d_tickets + q * LDPC_TICKET_STRIDE;
+  a.ticket_base = ctx->queues[q].base;
+  a.waves = 0;
+  a.static_stride = max_iters <= 10 ? 1 : 0;
+  ldpc::LayeredView v;
+  v.rows = ctx->d_lay_rows;
+  v.ci = ctx->d_lay_ci;
+  v.order = ctx->d_lay_order;
+  v.off = ctx->d_lay_off;
+  v.M = ctx->M;
+  v.N = ctx->N;
+  v.E = ctx->E;
+  v.KB = ctx->KB;
+  v.L = ctx->lay_L;
+  uint32_t advance = 0;
+  if (ldpc::launch_layered_decode(v, a, lay, scale, f32, st, ctx->lay_resident, &advance) != 0)
+    return hip_err(ctx, hipGetLastError(), "kernel launch");
+  ctx->queues[q].base += advance;
+  return LDPC_OK;
+}
+
 // Host-buffer decode (synchronous).  B_out = B (pm_half 0) or 2B (both
 // polarities).  The frames' samples are staged through a pinned buffer; for
 // an interleaved gr_complex stream (elem_stride 2, even cw_stride) only the
 // real parts are gathered and copied, and the kernel reads them densely.
+// layered_scale: the decode is ldpc_decode_layered's (method unused).
 int decode_host_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, int precision,
                      const float *in, int64_t n_in_floats, int64_t cw_stride, int elem_stride,
                      float polarity, int B, bool both, uint8_t *out_packed, uint8_t *out_bits_opt,
-                     int32_t *iters_used_opt, int32_t *syn_weight_opt, float *llr_out_opt) {
+                     int32_t *iters_used_opt, int32_t *syn_weight_opt, float *llr_out_opt,
+                     const double *layered_scale = nullptr) {
   serve_stop(ctx);
   int rc = check_decode_args(ctx, method, max_iters, et_period, precision, B, elem_stride,
                              cw_stride);
   if (rc != LDPC_OK) return rc;
+  // a layered decode that will be refused is refused before anything is staged
+  if (layered_scale && (rc = layered_ready(ctx, *layered_scale, precision)) != LDPC_OK)
+    return rc;
   if (B == 0) return LDPC_OK;
   if (!in || !out_packed) return set_err(ctx, LDPC_EINVAL, "null buffer");
   const int64_t span = (int64_t)(B - 1) * cw_stride + (int64_t)(ctx->N - 1) * elem_stride + 1;
@@ -1495,8 +1670,12 @@ int decode_host_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, in
   if ((e = hipMemcpyAsync(d_in, h, (size_t)n_stage * 4, hipMemcpyHostToDevice, ctx->stream)) !=
       hipSuccess)
     return hip_err(ctx, e, "hipMemcpyAsync(in)");
-  rc = decode_device_impl(ctx, method, max_iters, et_period, precision, d_in, cw, es, polarity,
-                          BO, both ? B : 0, d_pk, d_bits, d_it, d_sy, d_llr, ctx->stream);
+  if (layered_scale)
+    rc = layered_device_impl(ctx, *layered_scale, max_iters, et_period, precision, d_in, cw, es,
+                             polarity, BO, d_pk, d_bits, d_it, d_sy, d_llr, ctx->stream);
+  else
+    rc = decode_device_impl(ctx, method, max_iters, et_period, precision, d_in, cw, es, polarity,
+                            BO, both ? B : 0, d_pk, d_bits, d_it, d_sy, d_llr, ctx->stream);
   if (rc != LDPC_OK) return rc;
   if ((e = hipMemcpyAsync(h, d_pk, b_out, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
     return hip_err(ctx, e, "hipMemcpyAsync(out)");
@@ -2359,6 +2538,76 @@ int ldpc_decode(ldpc_ctx *ctx, int method, int max_iters, int et_period, int pre
   return ldpc_decode_strided(ctx, method, max_iters, et_period, precision, llr_re,
                              (int64_t)B * ctx->N, ctx->N, 1, 1.0f, B, out_packed, out_bits_opt,
                              iters_used_opt, syn_weight_opt, nullptr);
+}
+
+int ldpc_plan_layers(int M, int N, const int32_t *row_ptr, const int32_t *col_idx, int precision,
+                     int32_t *layer_of_row_out_opt, int *n_layers_out_opt,
+                     int64_t *lds_bytes_out_opt, int *threads_out_opt) {
+  g_create_error.clear();
+  if (!valid_csr(M, N, row_ptr, col_idx))
+    return set_err(nullptr, LDPC_EINVAL, "CSR H must be M x N (M < N), columns ascending and in range");
+  if (precision < 0 || precision > 3)
+    return set_err(nullptr, LDPC_EINVAL, "precision must be one of LDPC_PREC_*");
+  try {
+    std::vector<int32_t> plan;
+    const int L = ldpc::plan_layers(M, N, row_ptr, col_idx, plan);
+    int dc_max = 0;
+    for (int j = 0; j < M; ++j) dc_max = std::max(dc_max, row_ptr[j + 1] - row_ptr[j]);
+    ldpc::LayeredLayout lay;
+    const bool fits = ldpc::layered_layout(M, N, row_ptr[M], dc_max, L, largest_layer(plan, L),
+                                           precision, lay);
+    if (layer_of_row_out_opt) std::copy(plan.begin(), plan.end(), layer_of_row_out_opt);
+    if (n_layers_out_opt) *n_layers_out_opt = L;
+    if (lds_bytes_out_opt) *lds_bytes_out_opt = fits ? lay.total : lay.frame;
+    if (threads_out_opt) *threads_out_opt = lay.threads;
+    return fits ? 1 : 0;
+  } catch (const std::exception &e) {
+    return set_err(nullptr, LDPC_ENOMEM, e.what());
+  }
+}
+
+int ldpc_ctx_layers(const ldpc_ctx *ctx, int32_t *layer_of_row_out_opt) {
+  if (!ctx) return LDPC_EINVAL;
+  ensure_layer_plan(const_cast<ldpc_ctx *>(ctx));  // made on first use; contexts are never const objects
+  if (layer_of_row_out_opt)
+    std::copy(ctx->lay_of_row.begin(), ctx->lay_of_row.end(), layer_of_row_out_opt);
+  return ctx->lay_L;
+}
+
+int ldpc_set_layers(ldpc_ctx *ctx, const int32_t *layer_of_row) {
+  if (!ctx) return LDPC_EINVAL;
+  if (!layer_of_row) {
+    ctx->lay_L = 0;
+    ensure_layer_plan(ctx);
+    return LDPC_OK;
+  }
+  std::string why;
+  const int L = ldpc::check_layers(ctx->M, ctx->N, ctx->rp.data(), ctx->ci.data(), layer_of_row, &why);
+  if (L < 0) return set_err(ctx, LDPC_EINVAL, "bad layer plan: " + why);
+  ctx->lay_of_row.assign(layer_of_row, layer_of_row + ctx->M);
+  ctx->lay_L = L;
+  ctx->lay_ready = false;
+  return LDPC_OK;
+}
+
+int ldpc_decode_layered(ldpc_ctx *ctx, double scale, int max_iters, int et_period, int precision,
+                        const float *in, int64_t n_in_floats, int64_t cw_stride, int elem_stride,
+                        float polarity, int B, uint8_t *out_packed, uint8_t *out_bits_opt,
+                        int32_t *iters_used_opt, int32_t *syn_weight_opt, float *llr_out_opt) {
+  return decode_host_impl(ctx, LDPC_METHOD_LOGDOMAIN, max_iters, et_period, precision, in,
+                          n_in_floats, cw_stride, elem_stride, polarity, B, false, out_packed,
+                          out_bits_opt, iters_used_opt, syn_weight_opt, llr_out_opt, &scale);
+}
+
+int ldpc_decode_layered_device(ldpc_ctx *ctx, double scale, int max_iters, int et_period,
+                               int precision, const float *d_in, int64_t cw_stride,
+                               int elem_stride, float polarity, int B, uint8_t *d_out_packed,
+                               uint8_t *d_out_bits_opt, int32_t *d_iters_used_opt,
+                               int32_t *d_syn_weight_opt, float *d_llr_out_opt,
+                               void *hip_stream) {
+  return layered_device_impl(ctx, scale, max_iters, et_period, precision, d_in, cw_stride,
+                             elem_stride, polarity, B, d_out_packed, d_out_bits_opt,
+                             d_iters_used_opt, d_syn_weight_opt, d_llr_out_opt, hip_stream);
 }
 
 int ldpc_ctx_streams(ldpc_ctx *ctx, int n, void **streams_out) {

@@ -85,6 +85,13 @@ SIGNATURES = {
     "ldpc_ring_wait": (_i, [_vp, _i64]),
     "ldpc_ring_end": (_i, [_vp]),
     "ldpc_ring_info": (_i, [_vp, _i32p, _i32p]),
+    "ldpc_plan_layers": (_i, [_i, _i, _i32p, _i32p, _i, _i32p, _i32p, _i64p, _i32p]),
+    "ldpc_ctx_layers": (_i, [_vp, _i32p]),
+    "ldpc_set_layers": (_i, [_vp, _i32p]),
+    "ldpc_decode_layered": (_i, [_vp, ctypes.c_double, _i, _i, _i, _f32p, _i64, _i64, _i,
+                                 ctypes.c_float, _i, _u8p, _u8p, _i32p, _i32p, _f32p]),
+    "ldpc_decode_layered_device": (_i, [_vp, ctypes.c_double, _i, _i, _i, _vp, _i64, _i,
+                                        ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
@@ -204,6 +211,24 @@ def plan_onchip(M, N, E, dc_max, dv_max, method=METHOD_SUMPRODUCT, precision=PRE
                                          int(method), int(precision), ctypes.byref(lds),
                                          ctypes.byref(threads)))
     return dict(fits=bool(fits), lds_bytes=lds.value, threads=threads.value)
+
+
+def plan_layers(csr, precision=PREC_F64):
+    """ldpc_plan_layers (host only, no GPU) for csr = (M, N, row_ptr, col_idx):
+    dict with fits (the layered kernel takes the code at this precision),
+    layer_of_row (M,), n_layers, lds_bytes (LDS its workgroup declares: the
+    frame's state, plus the code's tables where they fit behind it; the frame's
+    state alone when the code does not fit) and threads (of the workgroup)."""
+    M, N, rp, ci = csr
+    rp = np.ascontiguousarray(rp, np.int32)
+    ci = np.ascontiguousarray(ci, np.int32)
+    plan = np.zeros(max(int(M), 1), np.int32)
+    L, lds, threads = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
+    fits = _check(lib().ldpc_plan_layers(int(M), int(N), _p(rp, _i32p), _p(ci, _i32p),
+                                         int(precision), _p(plan, _i32p), ctypes.byref(L),
+                                         ctypes.byref(lds), ctypes.byref(threads)))
+    return dict(fits=bool(fits), layer_of_row=plan[:M], n_layers=L.value, lds_bytes=lds.value,
+                threads=threads.value)
 
 
 class Decoder:
@@ -430,6 +455,64 @@ class Decoder:
                                         int(precision), d_in, int(cw_stride), int(elem_stride),
                                         float(polarity), int(B), d_packed, d_bits, d_iters,
                                         d_synd, d_llr, stream), self._ctx)
+
+    @property
+    def layers(self):
+        """ldpc_ctx_layers: the layer of every row (M,) in the layered
+        decoder's plan in force (the planner's until set_layers replaces it)."""
+        plan = np.zeros(self.M, np.int32)
+        _check(lib().ldpc_ctx_layers(self._ctx, _p(plan, _i32p)), self._ctx)
+        return plan
+
+    def set_layers(self, layer_of_row):
+        """ldpc_set_layers: a caller's plan (M layer indices; no two rows of a
+        layer may share a column), or None for the planner's.  A refused plan
+        raises and leaves the current one in force."""
+        if layer_of_row is not None:
+            layer_of_row = np.ascontiguousarray(layer_of_row, np.int32)
+            if layer_of_row.shape != (self.M,):
+                raise LdpcError("LDPC_EINVAL: a plan has one layer index per row (%d)" % self.M)
+        _check(lib().ldpc_set_layers(self._ctx, _p(layer_of_row, _i32p)), self._ctx)
+
+    def decode_layered(self, llr, scale=1.0, max_iters=50, et_period=1, precision=PREC_F64,
+                       polarity=1.0, cw_stride=None, elem_stride=1, B=None, want_bits=True,
+                       want_llr=False):
+        """ldpc_decode_layered: layered normalized min-sum of host float32
+        frames (synchronous); arguments and result as decode()."""
+        x = np.ascontiguousarray(llr, np.float32).reshape(-1)
+        if cw_stride is None:
+            cw_stride = self.N * elem_stride
+        if B is None:
+            B = x.size // cw_stride if cw_stride else 0
+        packed = np.zeros((B, self.KB), np.uint8)
+        bits = np.zeros((B, self.N), np.uint8) if want_bits else None
+        iters = np.zeros(B, np.int32)
+        synd = np.zeros(B, np.int32)
+        post = np.zeros((B, self.N), np.float32) if want_llr else None
+        _check(lib().ldpc_decode_layered(self._ctx, float(scale), int(max_iters), int(et_period),
+                                         int(precision), _p(x, _f32p), x.size, int(cw_stride),
+                                         int(elem_stride), float(polarity), int(B),
+                                         _p(packed, _u8p), _p(bits, _u8p), _p(iters, _i32p),
+                                         _p(synd, _i32p), _p(post, _f32p)), self._ctx)
+        out = dict(packed=packed, iters=iters, synd=synd)
+        if want_bits:
+            out["bits"] = bits
+        if want_llr:
+            out["llr"] = post
+        return out
+
+    def decode_layered_device(self, d_in, B, d_packed, scale=1.0, max_iters=50, et_period=1,
+                              precision=PREC_F64, polarity=1.0, cw_stride=None, elem_stride=1,
+                              d_bits=None, d_iters=None, d_synd=None, d_llr=None, stream=None):
+        """ldpc_decode_layered_device: enqueue a layered decode of
+        device-resident buffers (raw pointers / ints), as decode_device()."""
+        if cw_stride is None:
+            cw_stride = self.N * elem_stride
+        _check(lib().ldpc_decode_layered_device(self._ctx, float(scale), int(max_iters),
+                                                int(et_period), int(precision), d_in,
+                                                int(cw_stride), int(elem_stride), float(polarity),
+                                                int(B), d_packed, d_bits, d_iters, d_synd, d_llr,
+                                                stream), self._ctx)
 
     def set_launch_mode(self, mode):
         """MODE_LATENCY (default: one decode at a time) or MODE_THROUGHPUT

@@ -20,6 +20,12 @@ private copies.
 
     python -m ldpc_ece535a.ber [--frames 30] [--iterations 5]
                                [--ebn0 -7:10:0.5] [--code default|dvbs2] [--json out]
+                               [--layered SCALE]
+
+--layered SCALE adds a fifth curve, "LayeredMinSum": the layered normalized
+min-sum decoder (ldpc_decode_layered_device) at that scale, same iteration
+cap.  It is not one of the reference's decoders; without the option the
+output is the reference program's four curves.
 """
 import argparse
 import json
@@ -33,6 +39,7 @@ from . import _capi
 DEFAULT_EBN0 = [-7.0 + 0.5 * i for i in range(35)]  # :540
 METHODS = (("BPSK", _capi.METHOD_HARD), ("BitFlip", _capi.METHOD_BITFLIP),
            ("LogDomainSimple", _capi.METHOD_LOGDOMAIN), ("SumProduct", _capi.METHOD_SUMPRODUCT))
+LAYERED = "LayeredMinSum"
 
 
 def sigma_of(ebn0_db):
@@ -40,8 +47,10 @@ def sigma_of(ebn0_db):
     return math.sqrt(1.0 / math.exp(ebn0_db * math.log(10.0) / 10.0))
 
 
-def sweep(dec=None, ebn0=DEFAULT_EBN0, frames=30, iterations=5, seed=0, precision=0, device=0):
-    """Returns {method name: {"ber": [...], "fer": [...]}} over `ebn0`."""
+def sweep(dec=None, ebn0=DEFAULT_EBN0, frames=30, iterations=5, seed=0, precision=0, device=0,
+          layered_scale=None):
+    """Returns {method name: {"ber": [...], "fer": [...]}} over `ebn0`; with
+    layered_scale also LAYERED, the layered min-sum decoder at that scale."""
     import torch
     if dec is None:
         dec = _capi.Decoder(device=device)
@@ -56,17 +65,22 @@ def sweep(dec=None, ebn0=DEFAULT_EBN0, frames=30, iterations=5, seed=0, precisio
     d_err = torch.empty(B, dtype=torch.int32, device=dev)
     stream = torch.cuda.Stream(dev)
     sp = stream.cuda_stream
-    out = {name: {"ber": [], "fer": []} for name, _ in METHODS}
+    runs = list(METHODS) + ([(LAYERED, None)] if layered_scale is not None else [])
+    out = {name: {"ber": [], "fer": []} for name, _ in runs}
     for i, db in enumerate(ebn0):
         s0 = (int(seed) * 1000003 + i) & 0xFFFFFFFF
         _capi.random_bits(d_data.data_ptr(), B * K, s0, sp)
         dec.encode_device(d_data.data_ptr(), B, d_cw.data_ptr(), sp)
         _capi.bpsk_awgn(d_cw.data_ptr(), B * N, sigma_of(db), s0 ^ 0x5DEECE66D, d_tx.data_ptr(),
                         sp)
-        for name, m in METHODS:
-            dec.decode_device(d_tx.data_ptr(), B, d_packed.data_ptr(), method=m,
-                              max_iters=iterations, precision=precision, d_bits=d_bits.data_ptr(),
-                              d_synd=d_synd.data_ptr(), stream=sp)
+        for name, m in runs:
+            kw = dict(max_iters=iterations, precision=precision, d_bits=d_bits.data_ptr(),
+                      d_synd=d_synd.data_ptr(), stream=sp)
+            if m is None:
+                dec.decode_layered_device(d_tx.data_ptr(), B, d_packed.data_ptr(),
+                                          scale=layered_scale, **kw)
+            else:
+                dec.decode_device(d_tx.data_ptr(), B, d_packed.data_ptr(), method=m, **kw)
             _capi.count_bit_errors(d_bits.data_ptr(), d_cw.data_ptr(), N, B, d_err.data_ptr(), sp)
             stream.synchronize()
             err = d_err.cpu().numpy().astype(np.float64)
@@ -80,17 +94,18 @@ def octave(ebn0, res):
     """The reference program's Octave output (apps/ldpc_lapack.cpp:707-811)."""
     f = lambda v: "%.4g" % v  # noqa: E731  (std::cout.precision(4))
     lines = ["EbN0=[" + " ".join(f(x) for x in ebn0) + " ];", "figure(1);"]
-    styles = ["'or--'", "'og-'", "'ob-'", "'om-'"]
-    for k, (name, _) in enumerate(METHODS):
+    styles = ["'or--'", "'og-'", "'ob-'", "'om-'", "'ok-'"]
+    names = [name for name, _ in METHODS] + ([LAYERED] if LAYERED in res else [])
+    legend = "legend(" + ", ".join("'%s'" % n for n in names) + ");"
+    for k, name in enumerate(names):
         lines.append("ber%d=[" % k + " ".join(f(x) for x in res[name]["ber"]) + " ];")
         lines.append("plot(EbN0, ber%d, %s);" % (k, styles[k]))
         if k == 0:
             lines.append("hold;")
     lines += ["grid on;", "hold off;", "title('Bit Error Rate');",
-              "legend('BPSK', 'BitFlip', 'LogDomainSimple', 'SumProduct');",
-              "xlabel('EbN0');", "ylabel('BER');", "figure(2);"]
-    fstyles = ["'or:'", "'og-'", "'ob-'", "'om-'"]
-    for k, (name, _) in enumerate(METHODS):
+              legend, "xlabel('EbN0');", "ylabel('BER');", "figure(2);"]
+    fstyles = ["'or:'", "'og-'", "'ob-'", "'om-'", "'ok-'"]
+    for k, name in enumerate(names):
         lines.append("fer%d=[" % k)
         lines.append(", ".join(str(x) for x in res[name]["fer"]))  # printVector, :71-81
         lines.append("];")
@@ -98,8 +113,7 @@ def octave(ebn0, res):
         if k == 0:
             lines.append("hold;")
     lines += ["grid on;", "hold off;", "title('Frame Errors');",
-              "legend('BPSK', 'BitFlip', 'LogDomainSimple', 'SumProduct');",
-              "xlabel('EbN0');", "ylabel('FER');"]
+              legend, "xlabel('EbN0');", "ylabel('FER');"]
     return "\n".join(lines) + "\n"
 
 
@@ -121,6 +135,8 @@ def main(argv=None):
     ap.add_argument("--precision", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--layered", type=float, default=None, metavar="SCALE",
+                    help="add the layered normalized min-sum decoder at this scale (0 < SCALE <= 1)")
     a = ap.parse_args(argv)
     # torch first: it then shares its HIP runtime with libldpc_hip.so (see
     # INTEGRATION.md, "One HIP runtime per process")
@@ -131,7 +147,7 @@ def main(argv=None):
     else:
         dec = _capi.Decoder()
     grid = parse_range(a.ebn0)
-    res = sweep(dec, grid, a.frames, a.iterations, a.seed, a.precision)
+    res = sweep(dec, grid, a.frames, a.iterations, a.seed, a.precision, layered_scale=a.layered)
     sys.stdout.write(octave(grid, res))
     if a.json:
         json.dump({"ebn0": grid, "frames": a.frames, "iterations": a.iterations,

@@ -163,6 +163,24 @@ int ldpc_plan_storage_order(int M, int N, const int32_t *row_ptr, const int32_t 
 int ldpc_plan_onchip(int M, int N, int E, int dc_max, int dv_max, int method, int precision,
                      int64_t *lds_bytes_out_opt, int *threads_out_opt);
 
+/* The layered decoder's plan for a CSR H at `precision` (no GPU): first fit
+ * over the rows in ascending order -- row j goes to the lowest layer with which
+ * it shares no column -- so the rows of a layer share no column, every row is
+ * in one layer, and two calls give the same plan.  layer_of_row_out (M)
+ * receives the layer of every row, n_layers_out their number L, lds_bytes_out
+ * the LDS a workgroup declares -- one frame's state (N posteriors and E check
+ * messages as reals, N decision bytes, 128 bytes of reduction words) plus, where
+ * they fit behind it, the code's tables -- and threads_out the threads of the
+ * workgroup (the largest layer's rows rounded up to 64, at most 1024).  Returns
+ * 1 when the code fits the layered kernel (M, N, E <= 65535, check degrees <=
+ * 32, a frame's state within 163840 bytes), 0 when it does not (lds_bytes is
+ * then the frame's state alone), or a negative code for bad arguments
+ * (ldpc_last_error(NULL)).  (Replaces nothing in the reference, whose decoders
+ * all use the flooding schedule, lib/ldpc_decoder_cb_impl.cc:309-557.) */
+int ldpc_plan_layers(int M, int N, const int32_t *row_ptr, const int32_t *col_idx, int precision,
+                     int32_t *layer_of_row_out_opt, int *n_layers_out_opt,
+                     int64_t *lds_bytes_out_opt, int *threads_out_opt);
+
 /* ---- device context ----------------------------------------------- */
 
 /* Builds the decoder's view of H (reorderHMatrix unless
@@ -334,6 +352,55 @@ int ldpc_decode_device(ldpc_ctx *ctx, int method, int max_iters,
                        int B, uint8_t *d_out_packed, uint8_t *d_out_bits_opt,
                        int32_t *d_iters_used_opt, int32_t *d_syn_weight_opt,
                        float *d_llr_out_opt, void *hip_stream);
+
+/* Layered normalized min-sum: an opt-in decode algorithm of its own, beside the
+ * reference's methods (which keep their numbers and entry points).  The rows
+ * of the context's H are taken layer by layer (row-serial schedule), each row
+ * reading the posteriors the rows before it have updated, and every check
+ * message is multiplied by `scale` (0 < scale <= 1, finite; 1 = plain min-sum).
+ * Conventions are decodeLogDomainSimple's (lib/ldpc_decoder_cb_impl.cc:309-412):
+ * Lci = -tx, sign(0) = 0, the DBL_MAX (float: FLT_MAX) seed of the minimum,
+ * decision L(Q_i) < 0, and its exit rule (the cap first, then the syndrome on
+ * multiples of et_period).  Real = float for LDPC_PREC_F32, double otherwise.
+ * Per frame, LQ = (Real)(-tx), R = 0, then per iteration, for every layer in
+ * order and every row of it, with the row's edges e_k in ascending column c_k:
+ *   q_k = LQ[c_k] - R[e_k];  s_k = sign(q_k);  P = s_0 * ... * s_{d-1};
+ *   lo_k = the least |q_t| over t != k under strict < from the seed;
+ *   R[e_k] = scale * ((Real)(P * s_k) * lo_k);  LQ[c_k] = q_k + R[e_k]
+ * with no contraction: results are bit for bit those of that sequence.
+ * Outputs as for ldpc_decode_device; llr_out is (float)LQ.  One frame per
+ * persistent workgroup, LQ and R in LDS (csrc/ldpc_layered.hip).
+ *
+ *   ldpc_ctx_layers     the plan in force: copies the layer of every row (M
+ *                       ints, optional) and returns L.  The planner's
+ *                       (ldpc_plan_layers) until ldpc_set_layers replaces it.
+ *   ldpc_set_layers     a caller's plan, e.g. the block rows of a QC code:
+ *                       layer_of_row (M) in [0, M), no column twice in a layer;
+ *                       otherwise LDPC_EINVAL, the message naming the two rows
+ *                       and the column, and the plan in force stays.  NULL
+ *                       restores the planner's.
+ *   ldpc_decode_layered          host buffers, synchronous; parameters as
+ *                       ldpc_decode_strided with `scale` in place of `method`.
+ *   ldpc_decode_layered_device   device buffers, enqueued on hip_stream;
+ *                       parameters as ldpc_decode_device with `scale` in place
+ *                       of `method`.
+ * Both decode calls work on any context (default, LDPC_FLAG_GRAPH,
+ * LDPC_FLAG_ONCHIP) whose code fits (ldpc_plan_layers; LDPC_EUNSUPPORTED with
+ * the LDS a frame needs otherwise), build and upload their tables on first
+ * use and after a change of plan, end a running window server first, and
+ * return LDPC_EINVAL while a frame ring session is open. */
+int ldpc_ctx_layers(const ldpc_ctx *ctx, int32_t *layer_of_row_out_opt);
+int ldpc_set_layers(ldpc_ctx *ctx, const int32_t *layer_of_row);
+int ldpc_decode_layered(ldpc_ctx *ctx, double scale, int max_iters, int et_period, int precision,
+                        const float *in, int64_t n_in_floats, int64_t cw_stride, int elem_stride,
+                        float polarity, int B, uint8_t *out_packed, uint8_t *out_bits_opt,
+                        int32_t *iters_used_opt, int32_t *syn_weight_opt, float *llr_out_opt);
+int ldpc_decode_layered_device(ldpc_ctx *ctx, double scale, int max_iters, int et_period,
+                               int precision, const float *d_in, int64_t cw_stride,
+                               int elem_stride, float polarity, int B, uint8_t *d_out_packed,
+                               uint8_t *d_out_bits_opt, int32_t *d_iters_used_opt,
+                               int32_t *d_syn_weight_opt, float *d_llr_out_opt,
+                               void *hip_stream);
 
 /* The frame ring: ONE persistent launch decodes every batch posted to it
  * (small codes; min-sum and sum-product, any precision).  The frames of all
