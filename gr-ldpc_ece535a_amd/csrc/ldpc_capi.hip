@@ -27,6 +27,7 @@
 #include "ldpc_kernels.hpp"
 #include "ldpc_layout.hpp"
 #include "ldpc_layered.hpp"
+#include "ldpc_qc.hpp"
 #include "ldpc_onchip.hpp"
 
 using ldpc::ColRec;
@@ -216,6 +217,16 @@ struct ldpc_ctx {
   uint32_t *d_lay_rows = nullptr, *d_lay_off = nullptr;
   uint16_t *d_lay_ci = nullptr, *d_lay_order = nullptr;
   int lay_resident[2] = {0, 0};  // workgroups the device holds, f64 / f32 kernel
+  // a quasi-cyclic context (ldpc_create_qc) remembers its base matrix; its
+  // planner's plan is the block rows, and while that plan is in force (and
+  // LDPC_FLAG_QC_TABLES is not set) layered decodes run the circulant kernel
+  // (ldpc_layered_qc.hip) from the base tables d_qc_*
+  int qc_mb = 0, qc_nb = 0, qc_Z = 0;  // qc_Z == 0: not a QC context
+  std::vector<int32_t> qc_shifts;
+  bool qc_tables = false;   // LDPC_FLAG_QC_TABLES
+  bool lay_qc = false;      // the tables uploaded are the circulant kernel's
+  uint32_t *d_qc_rows = nullptr, *d_qc_ent = nullptr;
+  int qc_rows = 0;          // block rows in d_qc_rows (those with an entry)
   // device encoder (built on first ldpc_encode_device): 1 small (A = H_p^-1 H_d
   // bit rows in d_encA), 2 IRA staircase, -1 no systematic encoder
   int enc_kind = 0;
@@ -1079,28 +1090,15 @@ ldpc_ctx *finish_create(ldpc_ctx *ctx, int flags, int device) {
   return ctx;
 }
 
-}  // namespace
+// ldpc_create_csr and ldpc_create_qc (qc: the base matrix the CSR was expanded
+// from, which the context remembers): the same context either way.
+struct QcSpec {
+  int mb, nb, Z;
+  const int32_t *shifts;
+};
 
-extern "C" {
-
-ldpc_ctx *ldpc_create(const uint8_t *H, int M, int N, int flags, int device) {
-  g_create_error.clear();
-  if (!valid_h(H, M, N)) {
-    set_err(nullptr, LDPC_EINVAL, "H must be M x N (M < N) with 0/1 entries");
-    return nullptr;
-  }
-  ldpc_ctx *ctx = new ldpc_ctx();
-  ctx->M = M;
-  ctx->N = N;
-  ctx->H.assign(H, H + (size_t)M * N);
-  if (!(flags & LDPC_FLAG_NO_REORDER)) reorder_columns(ctx->H.data(), M, N, nullptr, nullptr, nullptr);
-  dense_to_csr(ctx->H.data(), M, N, ctx->rp, ctx->ci);
-  return finish_create(ctx, flags, device);
-}
-
-ldpc_ctx *ldpc_create_csr(int M, int N, const int32_t *row_ptr, const int32_t *col_idx,
-                          int flags, int device) {
-  g_create_error.clear();
+ldpc_ctx *create_from_csr(int M, int N, const int32_t *row_ptr, const int32_t *col_idx, int flags,
+                          const QcSpec *qc, int device) {
   if (!valid_csr(M, N, row_ptr, col_idx)) {
     set_err(nullptr, LDPC_EINVAL,
             "CSR H must be M x N (M < N), row_ptr[0] == 0, non-decreasing, columns ascending "
@@ -1117,7 +1115,65 @@ ldpc_ctx *ldpc_create_csr(int M, int N, const int32_t *row_ptr, const int32_t *c
     for (int j = 0; j < M; ++j)
       for (int32_t e = row_ptr[j]; e < row_ptr[j + 1]; ++e) ctx->H[(size_t)j * N + col_idx[e]] = 1;
   }
+  if (qc) {
+    ctx->qc_mb = qc->mb;
+    ctx->qc_nb = qc->nb;
+    ctx->qc_Z = qc->Z;
+    ctx->qc_shifts.assign(qc->shifts, qc->shifts + (size_t)qc->mb * qc->nb);
+    ctx->qc_tables = (flags & LDPC_FLAG_QC_TABLES) != 0;
+  }
   return finish_create(ctx, flags, device);
+}
+
+}  // namespace
+
+extern "C" {
+
+ldpc_ctx *ldpc_create(const uint8_t *H, int M, int N, int flags, int device) {
+  g_create_error.clear();
+  if (flags & LDPC_FLAG_QC_TABLES) {
+    set_err(nullptr, LDPC_EINVAL, "LDPC_FLAG_QC_TABLES belongs to ldpc_create_qc");
+    return nullptr;
+  }
+  if (!valid_h(H, M, N)) {
+    set_err(nullptr, LDPC_EINVAL, "H must be M x N (M < N) with 0/1 entries");
+    return nullptr;
+  }
+  ldpc_ctx *ctx = new ldpc_ctx();
+  ctx->M = M;
+  ctx->N = N;
+  ctx->H.assign(H, H + (size_t)M * N);
+  if (!(flags & LDPC_FLAG_NO_REORDER)) reorder_columns(ctx->H.data(), M, N, nullptr, nullptr, nullptr);
+  dense_to_csr(ctx->H.data(), M, N, ctx->rp, ctx->ci);
+  return finish_create(ctx, flags, device);
+}
+
+ldpc_ctx *ldpc_create_csr(int M, int N, const int32_t *row_ptr, const int32_t *col_idx,
+                          int flags, int device) {
+  g_create_error.clear();
+  if (flags & LDPC_FLAG_QC_TABLES) {
+    set_err(nullptr, LDPC_EINVAL, "LDPC_FLAG_QC_TABLES belongs to ldpc_create_qc");
+    return nullptr;
+  }
+  return create_from_csr(M, N, row_ptr, col_idx, flags, nullptr, device);
+}
+
+ldpc_ctx *ldpc_create_qc(int mb, int nb, int Z, const int32_t *shifts, int flags, int device) {
+  g_create_error.clear();
+  std::string why;
+  if (!ldpc::qc_check(mb, nb, Z, shifts, &why)) {
+    set_err(nullptr, LDPC_EINVAL, "bad quasi-cyclic code: " + why);
+    return nullptr;
+  }
+  try {
+    const QcSpec qc{mb, nb, Z, shifts};
+    std::vector<int32_t> rp, ci;
+    ldpc::qc_expand(mb, nb, Z, shifts, rp, ci);
+    return create_from_csr(mb * Z, nb * Z, rp.data(), ci.data(), flags, &qc, device);
+  } catch (const std::exception &e) {
+    set_err(nullptr, LDPC_ENOMEM, e.what());
+    return nullptr;
+  }
 }
 
 void ldpc_destroy(ldpc_ctx *ctx) {
@@ -1163,7 +1219,7 @@ void ldpc_destroy(ldpc_ctx *ctx) {
     if (p) (void)hipFree(p);
   for (uint16_t *p : {ctx->d_oc_ci, ctx->d_oc_ce, ctx->d_lay_ci, ctx->d_lay_order})
     if (p) (void)hipFree(p);
-  for (uint32_t *p : {ctx->d_lay_rows, ctx->d_lay_off})
+  for (uint32_t *p : {ctx->d_lay_rows, ctx->d_lay_off, ctx->d_qc_rows, ctx->d_qc_ent})
     if (p) (void)hipFree(p);
   for (int32_t *p : {ctx->d_rp, ctx->d_ci, ctx->d_cp, ctx->d_ce, ctx->d_cr})
     if (p) (void)hipFree(p);
@@ -1475,11 +1531,26 @@ int largest_layer(const std::vector<int32_t> &layer_of_row, int L) {
   return most;
 }
 
-// The context's plan: the planner's unless the caller has set one.  Host only.
+// The context's plan: the planner's -- on a quasi-cyclic context the block
+// rows -- unless the caller has set one.  Host only.
 void ensure_layer_plan(ldpc_ctx *ctx) {
   if (ctx->lay_L > 0) return;
-  ctx->lay_L = ldpc::plan_layers(ctx->M, ctx->N, ctx->rp.data(), ctx->ci.data(), ctx->lay_of_row);
+  if (ctx->qc_Z > 0) {
+    ctx->lay_of_row.resize((size_t)ctx->M);
+    for (int j = 0; j < ctx->M; ++j) ctx->lay_of_row[j] = j / ctx->qc_Z;
+    ctx->lay_L = ctx->qc_mb;
+  } else {
+    ctx->lay_L = ldpc::plan_layers(ctx->M, ctx->N, ctx->rp.data(), ctx->ci.data(), ctx->lay_of_row);
+  }
   ctx->lay_ready = false;
+}
+
+// The plan in force is the block rows of a quasi-cyclic context, whoever set it.
+bool block_row_plan(const ldpc_ctx *ctx) {
+  if (ctx->qc_Z <= 0 || ctx->lay_L != ctx->qc_mb) return false;
+  for (int j = 0; j < ctx->M; ++j)
+    if (ctx->lay_of_row[j] != j / ctx->qc_Z) return false;
+  return true;
 }
 
 // Builds and uploads the layered decoder's tables from the context's CSR and
@@ -1501,14 +1572,26 @@ int prepare_layered(ldpc_ctx *ctx) {
              ldpc::kLayeredIndexMax, ldpc::kLayeredDcMax, ctx->M, ctx->N, ctx->E, ctx->dc_max);
     return set_err(ctx, LDPC_EUNSUPPORTED, buf);
   }
+  // the circulant kernel while the block rows of a quasi-cyclic context are
+  // the plan; the per-edge tables for any other plan and under LDPC_FLAG_QC_TABLES
+  const bool qc = !ctx->qc_tables && block_row_plan(ctx);
   ldpc::LayeredTables t;
-  ldpc::layered_build(ctx->M, ctx->rp.data(), ctx->ci.data(), ctx->lay_of_row, ctx->lay_L, t);
+  ldpc::QcTables qt;
+  if (qc) {
+    ldpc::qc_build(ctx->qc_mb, ctx->qc_nb, ctx->qc_Z, ctx->qc_shifts.data(), qt);
+    for (ldpc::LayeredLayout *lay : {&ctx->lay_f64, &ctx->lay_f32}) {
+      lay->staged = 0;  // the base tables are read through the scalar cache
+      lay->total = lay->frame;
+    }
+  } else {
+    ldpc::layered_build(ctx->M, ctx->rp.data(), ctx->ci.data(), ctx->lay_of_row, ctx->lay_L, t);
+  }
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
   // decodes that read the previous plan's tables may still run (any stream)
-  if (ctx->d_lay_rows && (e = hipDeviceSynchronize()) != hipSuccess)
+  if ((ctx->d_lay_rows || ctx->d_qc_rows) && (e = hipDeviceSynchronize()) != hipSuccess)
     return hip_err(ctx, e, "hipDeviceSynchronize");
-  for (uint32_t **p : {&ctx->d_lay_rows, &ctx->d_lay_off})
+  for (uint32_t **p : {&ctx->d_lay_rows, &ctx->d_lay_off, &ctx->d_qc_rows, &ctx->d_qc_ent})
     if (*p) {
       (void)hipFree(*p);
       *p = nullptr;
@@ -1519,16 +1602,23 @@ int prepare_layered(ldpc_ctx *ctx) {
       *p = nullptr;
     }
   const char *what = nullptr;
-  upload(ctx, &ctx->d_lay_rows, t.rows, "upload(layered rows)", what, e);
-  upload(ctx, &ctx->d_lay_ci, t.ci, "upload(layered col_idx)", what, e);
-  upload(ctx, &ctx->d_lay_order, t.order, "upload(layered row order)", what, e);
-  upload(ctx, &ctx->d_lay_off, t.off, "upload(layer offsets)", what, e);
+  if (qc) {
+    upload(ctx, &ctx->d_qc_rows, qt.rows, "upload(base rows)", what, e);
+    upload(ctx, &ctx->d_qc_ent, qt.ent, "upload(base entries)", what, e);
+  } else {
+    upload(ctx, &ctx->d_lay_rows, t.rows, "upload(layered rows)", what, e);
+    upload(ctx, &ctx->d_lay_ci, t.ci, "upload(layered col_idx)", what, e);
+    upload(ctx, &ctx->d_lay_order, t.order, "upload(layered row order)", what, e);
+    upload(ctx, &ctx->d_lay_off, t.off, "upload(layer offsets)", what, e);
+  }
   if (!what && !ctx->d_tickets) {  // large-code contexts have no frame queues of their own
     std::vector<uint32_t> zeros((size_t)LDPC_TICKET_SLOTS * LDPC_TICKET_STRIDE, 0);
     upload(ctx, &ctx->d_tickets, zeros, "upload(tickets)", what, e);
   }
   if (what) return hip_err(ctx, e, what);
-  ctx->lay_resident[0] = ctx->lay_resident[1] = 0;  // the layout's threads and bytes may differ
+  ctx->lay_resident[0] = ctx->lay_resident[1] = 0;  // the kernel, its threads and bytes may differ
+  ctx->lay_qc = qc;
+  ctx->qc_rows = (int)qt.rows.size();
   ctx->lay_ready = true;
   return LDPC_OK;
 }
@@ -1597,19 +1687,34 @@ int layered_device_impl(ldpc_ctx *ctx, double scale, int max_iters, int et_perio
   a.ticket_base = ctx->queues[q].base;
   a.waves = 0;
   a.static_stride = max_iters <= 10 ? 1 : 0;
-  ldpc::LayeredView v;
-  v.rows = ctx->d_lay_rows;
-  v.ci = ctx->d_lay_ci;
-  v.order = ctx->d_lay_order;
-  v.off = ctx->d_lay_off;
-  v.M = ctx->M;
-  v.N = ctx->N;
-  v.E = ctx->E;
-  v.KB = ctx->KB;
-  v.L = ctx->lay_L;
   uint32_t advance = 0;
-  if (ldpc::launch_layered_decode(v, a, lay, scale, f32, st, ctx->lay_resident, &advance) != 0)
-    return hip_err(ctx, hipGetLastError(), "kernel launch");
+  int launched;
+  if (ctx->lay_qc) {
+    ldpc::LayeredQcView v;
+    v.rows = ctx->d_qc_rows;
+    v.ent = ctx->d_qc_ent;
+    v.M = ctx->M;
+    v.N = ctx->N;
+    v.E = ctx->E;
+    v.KB = ctx->KB;
+    v.mb = ctx->qc_rows;
+    v.Z = ctx->qc_Z;
+    launched = ldpc::launch_layered_qc_decode(v, a, lay, scale, f32, st, ctx->lay_resident,
+                                              &advance);
+  } else {
+    ldpc::LayeredView v;
+    v.rows = ctx->d_lay_rows;
+    v.ci = ctx->d_lay_ci;
+    v.order = ctx->d_lay_order;
+    v.off = ctx->d_lay_off;
+    v.M = ctx->M;
+    v.N = ctx->N;
+    v.E = ctx->E;
+    v.KB = ctx->KB;
+    v.L = ctx->lay_L;
+    launched = ldpc::launch_layered_decode(v, a, lay, scale, f32, st, ctx->lay_resident, &advance);
+  }
+  if (launched != 0) return hip_err(ctx, hipGetLastError(), "kernel launch");
   ctx->queues[q].base += advance;
   return LDPC_OK;
 }
@@ -2588,6 +2693,45 @@ int ldpc_set_layers(ldpc_ctx *ctx, const int32_t *layer_of_row) {
   ctx->lay_L = L;
   ctx->lay_ready = false;
   return LDPC_OK;
+}
+
+int ldpc_plan_qc(int mb, int nb, int Z, const int32_t *shifts, int precision,
+                 int32_t *row_ptr_out_opt, int32_t *col_idx_out_opt, int64_t *lds_bytes_out_opt,
+                 int *threads_out_opt) {
+  g_create_error.clear();
+  std::string why;
+  if (!ldpc::qc_check(mb, nb, Z, shifts, &why))
+    return set_err(nullptr, LDPC_EINVAL, "bad quasi-cyclic code: " + why);
+  if (precision < 0 || precision > 3)
+    return set_err(nullptr, LDPC_EINVAL, "precision must be one of LDPC_PREC_*");
+  try {
+    int entries, row_max;
+    ldpc::qc_count(mb, nb, shifts, entries, row_max);
+    if (row_ptr_out_opt || col_idx_out_opt) {
+      std::vector<int32_t> rp, ci;
+      ldpc::qc_expand(mb, nb, Z, shifts, rp, ci);
+      if (row_ptr_out_opt) std::copy(rp.begin(), rp.end(), row_ptr_out_opt);
+      if (col_idx_out_opt) std::copy(ci.begin(), ci.end(), col_idx_out_opt);
+    }
+    // the block rows as a plan: mb layers of Z rows; nothing staged behind the frame
+    ldpc::LayeredLayout lay;
+    const bool fits = ldpc::layered_layout(mb * Z, nb * Z, entries * Z, row_max, mb, Z, precision, lay);
+    if (lds_bytes_out_opt) *lds_bytes_out_opt = lay.frame;
+    if (threads_out_opt) *threads_out_opt = lay.threads;
+    return fits ? 1 : 0;
+  } catch (const std::exception &e) {
+    return set_err(nullptr, LDPC_ENOMEM, e.what());
+  }
+}
+
+int ldpc_ctx_qc(const ldpc_ctx *ctx, int *mb, int *nb, int *Z, int32_t *shifts_out_opt) {
+  if (!ctx) return LDPC_EINVAL;
+  if (mb) *mb = ctx->qc_mb;
+  if (nb) *nb = ctx->qc_nb;
+  if (Z) *Z = ctx->qc_Z;
+  if (ctx->qc_Z <= 0) return 0;
+  if (shifts_out_opt) std::copy(ctx->qc_shifts.begin(), ctx->qc_shifts.end(), shifts_out_opt);
+  return 1;
 }
 
 int ldpc_decode_layered(ldpc_ctx *ctx, double scale, int max_iters, int et_period, int precision,

@@ -26,32 +26,13 @@
 // one kernel.
 #include <hip/hip_runtime.h>
 
-#include <float.h>
-
 #include <algorithm>
 
 #include "ldpc_layered.hpp"
+#include "ldpc_layered_dev.hpp"
 
 namespace ldpc {
 namespace {
-
-template <typename Real>
-struct Lim;
-template <>
-struct Lim<double> {
-  static __device__ __forceinline__ double big() { return DBL_MAX; }
-  static __device__ __forceinline__ double abs_(double x) { return ::fabs(x); }
-};
-template <>
-struct Lim<float> {
-  static __device__ __forceinline__ float big() { return FLT_MAX; }
-  static __device__ __forceinline__ float abs_(float x) { return ::fabsf(x); }
-};
-
-template <typename Real>
-__device__ __forceinline__ int ly_sgn(Real v) {
-  return (v > Real(0)) - (v < Real(0));
-}
 
 struct LyTabs {
   const uint32_t *rows;
@@ -72,9 +53,8 @@ __device__ __forceinline__ void ly_copy(T *dst, const T *src, int n) {
 constexpr int kRowRegs = 8;
 
 // Syndrome weight of the decisions LQ < 0 (checkFrame :236-253, no
-// threshold), read from the posteriors in LDS: every thread gets the sum.
-// One barrier; the layers' barriers separate this call's reads of red[] from
-// the next call's writes.
+// threshold), read from the posteriors in LDS: every thread gets the sum
+// (ly_sum_waves: one barrier).
 template <typename Real>
 __device__ __forceinline__ int ly_syndrome(const LyTabs &g, int M, const Real *LQ, int *red) {
   const int tid = threadIdx.x, T = blockDim.x;
@@ -97,12 +77,7 @@ __device__ __forceinline__ int ly_syndrome(const LyTabs &g, int M, const Real *L
     }
     cnt += __popcll(__ballot(odd));
   }
-  if ((tid & 63) == 0) red[tid >> 6] = cnt;
-  __syncthreads();
-  int w = 0;
-  const int nwaves = T >> 6;
-  for (int i = 0; i < nwaves; ++i) w += red[i];
-  return w;
+  return ly_sum_waves(cnt, red);
 }
 
 template <typename Real, bool STAGED>
@@ -139,20 +114,7 @@ __global__ void __launch_bounds__(kLayeredMaxThreads)
 
   int64_t b = blockIdx.x;
   while (b < a.B) {
-    // the layered entry points take strided frames only (no window lists, no
-    // second-polarity half: DecodeArgs::win and pm_half are unset)
-    const float pol = a.polarity;
-    const float *src = a.in + b * a.cw_stride;
-    // LQ = Lci = -tx, tx = in * polarity (:149-153, :318-321)
-    for (int i = tid; i < N; i += T) {
-      float tx = src[(int64_t)i * a.elem_stride] * pol;
-      // two operations: folded into one multiply by -polarity, a NaN sample
-      // would keep the sign that negating tx flips
-      asm volatile("" : "+v"(tx));
-      LQ[i] = (Real)(-tx);
-    }
-    for (int e = tid; e < E; e += T) R[e] = Real(0);
-    __syncthreads();
+    ly_load_frame(a, b, N, E, LQ, R);
     int used = 0, weight = 0;
     for (int h = 0;; ++h) {
       for (int l = 0; l < NL; ++l) {
@@ -228,34 +190,8 @@ __global__ void __launch_bounds__(kLayeredMaxThreads)
         if (last || weight == 0) break;
       }
     }
-    // the returned decisions (the syndrome's barrier is behind every LQ write)
-    for (int i = tid; i < N; i += T) hard[i] = LQ[i] < Real(0);
-    __syncthreads();
-    if (tid == 0) {
-      if (a.iters) a.iters[b] = used;
-      if (a.synd) a.synd[b] = weight;
-    }
-    if (a.bits)
-      for (int i = tid; i < N; i += T) a.bits[b * N + i] = hard[i];
-    if (a.llr)
-      for (int i = tid; i < N; i += T) a.llr[b * N + i] = (float)LQ[i];
-    for (int p = tid; p < gv.KB; p += T) {  // info bits M.., MSB first (:207-219)
-      uint32_t o = 0;
-      for (int j = 0; j < 8; ++j) {
-        const int c = M + 8 * p + j;
-        if (c < N) o |= (uint32_t)hard[c] << (7 - j);
-      }
-      a.packed[b * gv.KB + p] = (uint8_t)o;
-    }
-    // next frame (the barrier also ends this frame's LDS reads)
-    if (a.static_stride) {
-      __syncthreads();
-      b += a.waves;
-    } else {
-      if (tid == 0) red[16] = (int)(atomicAdd(a.ticket, 1u) - a.ticket_base);
-      __syncthreads();
-      b = (int64_t)a.waves + (int64_t)red[16];
-    }
+    ly_store_frame(a, b, M, N, gv.KB, used, weight, LQ, hard);
+    b = ly_next_frame(a, b, red);
   }
 }
 
@@ -263,21 +199,7 @@ template <typename Real, bool STAGED>
 int launch_kernel(const LayeredView &g, DecodeArgs a, const LayeredLayout &lay, double scale,
                   hipStream_t st, int &resident) {
   const void *fn = (const void *)layered_decode_kernel<Real, STAGED>;
-  if (resident == 0) {
-    // the attribute belongs to the kernel, not to this code: allow any layout
-    // layered_layout accepts
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLayeredLdsLimit) !=
-        hipSuccess)
-      return -3;
-    int per_cu = 0, dev = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, lay.threads,
-                                                     (size_t)lay.total) != hipSuccess ||
-        per_cu < 1 || hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus < 1)
-      return -3;
-    resident = per_cu * cus;
-  }
+  if (!ly_resident(fn, lay.threads, lay.total, resident)) return -3;
   a.waves = (int)std::min<int64_t>(a.B, resident);
   hipLaunchKernelGGL((layered_decode_kernel<Real, STAGED>), dim3((unsigned)a.waves),
                      dim3((unsigned)lay.threads), (size_t)lay.total, st, g, a, lay, (Real)scale);

@@ -30,4 +30,19 @@ int launch_layered_decode(const LayeredView &g, const DecodeArgs &args, const La
                           double scale, int prec, void *stream, int *resident,
                           uint32_t *advance_out);
 
+// A quasi-cyclic code as the circulant kernel reads it (ldpc_qc.hpp QcTables).
+struct LayeredQcView {
+  const uint32_t *rows;  // mb: degree (>= 1) | entries before << 16, per block row that has any
+  const uint32_t *ent;   // per base entry: block column * Z | shift << 16; 16 zero words behind
+  int M, N, E, KB, mb, Z;  // mb: the block rows listed in `rows`
+};
+
+// The same launch for a quasi-cyclic code decoded by its block rows
+// (ldpc_layered_qc.hip): `lay` is layered_layout's for mb layers of Z rows,
+// with nothing staged (lay.total == lay.frame: the base tables are read
+// through the scalar cache).  Arguments and result as launch_layered_decode.
+int launch_layered_qc_decode(const LayeredQcView &g, const DecodeArgs &args,
+                             const LayeredLayout &lay, double scale, int prec, void *stream,
+                             int *resident, uint32_t *advance_out);
+
 }  // namespace ldpc

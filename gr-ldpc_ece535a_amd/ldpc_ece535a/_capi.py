@@ -20,6 +20,7 @@ FLAG_NO_REORDER = 1
 FLAG_GRAPH = 2
 FLAG_PLAIN_LAYOUT = 4
 FLAG_ONCHIP = 8
+FLAG_QC_TABLES = 16
 TEST_SERVE_UNCHECKED, TEST_SERVE_EPOCH, TEST_SERVE_EPOCH_NOW, TEST_STREAM_OVERLAP = 1, 2, 3, 4
 SERVE_EPOCH_LIMIT = (1 << 23) - (1 << 16)
 PATH_SMALL, PATH_GRAPH, PATH_ONCHIP = 0, 1, 2
@@ -86,6 +87,9 @@ SIGNATURES = {
     "ldpc_ring_end": (_i, [_vp]),
     "ldpc_ring_info": (_i, [_vp, _i32p, _i32p]),
     "ldpc_plan_layers": (_i, [_i, _i, _i32p, _i32p, _i, _i32p, _i32p, _i64p, _i32p]),
+    "ldpc_plan_qc": (_i, [_i, _i, _i, _i32p, _i, _i32p, _i32p, _i64p, _i32p]),
+    "ldpc_create_qc": (_vp, [_i, _i, _i, _i32p, _i, _i]),
+    "ldpc_ctx_qc": (_i, [_vp, _i32p, _i32p, _i32p, _i32p]),
     "ldpc_ctx_layers": (_i, [_vp, _i32p]),
     "ldpc_set_layers": (_i, [_vp, _i32p]),
     "ldpc_decode_layered": (_i, [_vp, ctypes.c_double, _i, _i, _i, _f32p, _i64, _i64, _i,
@@ -231,6 +235,37 @@ def plan_layers(csr, precision=PREC_F64):
                 threads=threads.value)
 
 
+def _qc_base(base, Z):
+    """A base matrix as a contiguous (mb, nb) int32 array, with Z as an int."""
+    base = np.ascontiguousarray(base, np.int32)
+    if base.ndim != 2:
+        raise LdpcError("LDPC_EINVAL: a base matrix is two-dimensional (mb, nb)")
+    return base, int(Z)
+
+
+def plan_qc(base, Z, precision=PREC_F64):
+    """ldpc_plan_qc (host only, no GPU) for the quasi-cyclic code of base
+    matrix `base` ((mb, nb) shifts, -1 = no circulant) and lifting size Z: dict
+    with fits (the circulant kernel takes the code at this precision),
+    lds_bytes (LDS its workgroup declares: one frame's state), threads (of the
+    workgroup, 64 * ceil(Z / 64)) and csr = (M, N, row_ptr, col_idx), the
+    expanded H."""
+    base, Z = _qc_base(base, Z)
+    mb, nb = base.shape
+    ok = mb >= 1 and nb >= 1 and 1 <= Z <= 1024 and ((base >= -1) & (base < Z)).all()
+    M, N, E = (mb * Z, nb * Z, Z * int((base >= 0).sum())) if ok else (0, 0, 0)
+    rp = np.zeros(M + 1, np.int32)
+    ci = np.zeros(max(E, 1), np.int32)
+    lds, threads = ctypes.c_int64(0), ctypes.c_int32(0)
+    # a description the library refuses gets no buffers: it raises before it writes
+    fits = _check(lib().ldpc_plan_qc(mb, nb, Z, _p(base, _i32p), int(precision),
+                                     _p(rp, _i32p) if ok else None,
+                                     _p(ci, _i32p) if ok else None, ctypes.byref(lds),
+                                     ctypes.byref(threads)))
+    return dict(fits=bool(fits), lds_bytes=lds.value, threads=threads.value,
+                csr=(M, N, rp, ci[:E]))
+
+
 class Decoder:
     """One decode context (device tables + stream) for one H.
 
@@ -241,13 +276,25 @@ class Decoder:
     small-code kernel's edges and columns in CSR order (A/B and tests);
     onchip=True runs min-sum / sum-product on the on-chip kernels (one frame
     per workgroup, messages in LDS; path == PATH_ONCHIP) for any code that
-    fits them (plan_onchip), and raises for one that does not."""
+    fits them (plan_onchip), and raises for one that does not.
+    qc=(base, Z) builds the context of a quasi-cyclic code from its base matrix
+    ((mb, nb) shifts, -1 = no circulant) and lifting size: the context
+    Decoder(csr=plan_qc(base, Z)["csr"]) would be, except that its layered
+    decodes take the block rows as their plan and, while that plan is in force,
+    run the circulant kernel; qc_tables=True keeps the plan and runs the
+    per-edge table kernel (A/B and tests)."""
 
     def __init__(self, H=None, reorder=True, device=0, csr=None, force_graph=False,
-                 plain_layout=False, onchip=False):
+                 plain_layout=False, onchip=False, qc=None, qc_tables=False):
         flags = ((0 if reorder else FLAG_NO_REORDER) | (FLAG_GRAPH if force_graph else 0) |
-                 (FLAG_PLAIN_LAYOUT if plain_layout else 0) | (FLAG_ONCHIP if onchip else 0))
-        if csr is not None:
+                 (FLAG_PLAIN_LAYOUT if plain_layout else 0) | (FLAG_ONCHIP if onchip else 0) |
+                 (FLAG_QC_TABLES if qc_tables else 0))
+        if qc is not None:
+            base, Z = _qc_base(*qc)
+            self._ctx = lib().ldpc_create_qc(base.shape[0], base.shape[1], Z, _p(base, _i32p),
+                                             flags, int(device))
+            what = "ldpc_create_qc"
+        elif csr is not None:
             M, N, rp, ci = csr
             rp = np.ascontiguousarray(rp, np.int32)
             ci = np.ascontiguousarray(ci, np.int32)
@@ -272,6 +319,17 @@ class Decoder:
         _check(lib().ldpc_ctx_csr(self._ctx, _p(self.row_ptr, _i32p), _p(self.col_idx, _i32p)),
                self._ctx)
         self._H = None
+
+    @property
+    def qc(self):
+        """ldpc_ctx_qc: (base, Z) of a quasi-cyclic context (base: the (mb, nb)
+        shifts), None for any other."""
+        v = [ctypes.c_int32(0) for _ in range(3)]
+        if not _check(lib().ldpc_ctx_qc(self._ctx, *[ctypes.byref(x) for x in v], None), self._ctx):
+            return None
+        base = np.zeros((v[0].value, v[1].value), np.int32)
+        _check(lib().ldpc_ctx_qc(self._ctx, None, None, None, _p(base, _i32p)), self._ctx)
+        return base, v[2].value
 
     def pipeline(self):
         """ldpc_ctx_pipeline: {frames_per_chunk, chunks} of the large-code
@@ -459,7 +517,8 @@ class Decoder:
     @property
     def layers(self):
         """ldpc_ctx_layers: the layer of every row (M,) in the layered
-        decoder's plan in force (the planner's until set_layers replaces it)."""
+        decoder's plan in force (the planner's -- on a quasi-cyclic context
+        the block rows -- until set_layers replaces it)."""
         plan = np.zeros(self.M, np.int32)
         _check(lib().ldpc_ctx_layers(self._ctx, _p(plan, _i32p)), self._ctx)
         return plan

@@ -115,6 +115,68 @@ def syndrome_weight(csr, bits):
     return out
 
 
+# ---- quasi-cyclic codes ---------------------------------------------------------
+#
+# A base matrix of circulant shifts (mb, nb) and a lifting size Z (Decoder(qc=...),
+# ldpc_create_qc): -1 is the zero block, s in [0, Z) the identity rotated by s.
+# No standard base graph is available offline; qc_dual_diagonal() draws one with
+# the dual-diagonal parity part of the 802.11n / 802.16e families from a seed.
+# Results on it are labelled "QC dual-diagonal (synthetic base matrix)".
+
+def qc_expand(base, Z):
+    """CSR (M, N, row_ptr, col_idx) of the code of base matrix `base` lifted by
+    Z: row r*Z + i has a one in column c*Z + (i + s) mod Z for every entry
+    base[r, c] = s >= 0."""
+    base = np.asarray(base, np.int64)
+    Z = int(Z)
+    if base.ndim != 2 or Z < 1 or (base < -1).any() or (base >= Z).any():
+        raise ValueError("base must be (mb, nb) with entries in [-1, Z)")
+    mb, nb = base.shape
+    br, bc = np.nonzero(base >= 0)
+    i = np.arange(Z, dtype=np.int64)
+    r = (br[:, None] * Z + i).reshape(-1)
+    c = (bc[:, None] * Z + (i + base[br, bc][:, None]) % Z).reshape(-1)
+    order = np.lexsort((c, r))
+    row_ptr = np.zeros(mb * Z + 1, np.int64)
+    np.add.at(row_ptr, r + 1, 1)
+    return mb * Z, nb * Z, np.cumsum(row_ptr).astype(np.int32), c[order].astype(np.int32)
+
+
+def qc_dual_diagonal(mb, nb, Z, info_deg, seed):
+    """Seeded (mb, nb) base matrix: the parity part (block columns 0..mb-1) is
+    the diagonal and the sub-diagonal at shift 0, and every information block
+    column (mb..nb-1) has min(info_deg, mb) circulants in distinct block rows
+    with shifts drawn from [0, Z)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    S = np.full((mb, nb), -1, np.int32)
+    for r in range(mb):
+        S[r, r] = 0
+        if r >= 1:
+            S[r, r - 1] = 0
+    for c in range(mb, nb):
+        rows = rng.choice(mb, size=min(info_deg, mb), replace=False)
+        S[rows, c] = rng.integers(0, Z, size=rows.size)
+    return S
+
+
+def qc_encode(csr, info_bits):
+    """Systematic encoding of a code whose parity part (columns 0..M-1) is
+    lower triangular with a unit diagonal, as qc_dual_diagonal's is: (B, K)
+    info bits -> (B, N) codewords [parity | info], parity bit j, for j
+    ascending, the mod-2 sum of the other columns of row j."""
+    M, N, row_ptr, col_idx = csr
+    info = np.atleast_2d(np.asarray(info_bits, np.uint8)) & 1
+    cw = np.concatenate([np.zeros((info.shape[0], M), np.uint8), info], axis=1)
+    for j in range(M):
+        cols = np.asarray(col_idx[row_ptr[j]:row_ptr[j + 1]], np.int64)
+        if not (cols == j).any() or ((cols < M) & (cols > j)).any():
+            raise ValueError("row %d: the parity part is not lower triangular with a unit "
+                             "diagonal" % j)
+        cw[:, j] = np.bitwise_xor.reduce(cw[:, cols[cols != j]], axis=1) if cols.size > 1 else 0
+    assert not syndrome_weight(csr, cw).any()
+    return cw
+
+
 def alist_text(H=None, csr=None, padded=True):
     """MacKay alist text of a dense H (M, N) or a CSR (M, N, row_ptr, col_idx):
     "N M", the maximum column / row degrees, the degrees, then each column's

@@ -7,11 +7,12 @@
  * functions.  Each entry point below names the reference interface it
  * replaces (paths relative to the reference repository root):
  *
- *   ldpc_create / ldpc_create_csr / ldpc_destroy
+ *   ldpc_create / ldpc_create_csr / ldpc_create_qc / ldpc_destroy
  *       ldpc_decoder_cb_impl::ldpc_decoder_cb_impl(method)
  *       lib/ldpc_decoder_cb_impl.cc:35-117 (H setup + reorderHMatrix :104-106);
  *       ldpc_create_csr takes H as a sparse row list, for codes whose dense
- *       M x N matrix the reference could not hold
+ *       M x N matrix the reference could not hold,
+ *       ldpc_create_qc as a quasi-cyclic base matrix
  *   ldpc_decode, ldpc_decode_strided, ldpc_decode_strided_both, ldpc_decode_windows,
  *   ldpc_serve_begin / ldpc_serve_windows / ldpc_serve_end, ldpc_decode_device
  *       decodeLogDomainSimple :309-412, decodeSumProductSoft :478-557,
@@ -84,6 +85,9 @@ extern "C" {
                                   code that fits them (ldpc_plan_onchip), small
                                   ones included; LDPC_EUNSUPPORTED otherwise,
                                   LDPC_EINVAL together with LDPC_FLAG_GRAPH */
+#define LDPC_FLAG_QC_TABLES 16 /* ldpc_create_qc only (LDPC_EINVAL elsewhere):
+                                  layered decodes keep the block-row plan but run
+                                  the per-edge table kernel (A/B, cross-check) */
 
 /* error codes */
 #define LDPC_OK 0
@@ -181,6 +185,30 @@ int ldpc_plan_layers(int M, int N, const int32_t *row_ptr, const int32_t *col_id
                      int32_t *layer_of_row_out_opt, int *n_layers_out_opt,
                      int64_t *lds_bytes_out_opt, int *threads_out_opt);
 
+/* A quasi-cyclic code (no GPU): `shifts` is the mb x nb base matrix, row-major;
+ * -1 is the zero block and s in [0, Z) the Z x Z identity rotated by s, so row
+ * r * Z + i of H has a one in column c * Z + (i + s) mod Z for every base entry
+ * (r, c) with s >= 0 (one circulant per cell).  Writes the expanded H as CSR
+ * when the pointers are given: M = mb * Z rows, N = nb * Z columns, E = Z *
+ * (base entries >= 0) ones, row_ptr_out (M + 1), col_idx_out (E), the columns
+ * of every row strictly ascending.  The block rows are a layer plan
+ * (layer_of_row[j] = j / Z); threads_out receives the workgroup's threads,
+ * 64 * ceil(Z / 64) (a thread per row of a block row), and lds_bytes_out the
+ * LDS the circulant kernel declares:
+ *   a16(N * sizeof(Real)) + a16(E * sizeof(Real)) + a16(N) + 128,
+ * a16 rounding up to 16 bytes, Real = float for LDPC_PREC_F32 and double
+ * otherwise: one frame's state, as for ldpc_plan_layers, and nothing behind it
+ * (the kernel keeps no table in LDS: its base table, one word per base row and
+ * per base entry, is read with scalar loads).  Returns 1 when the circulant
+ * kernel takes the code at this precision (base row degrees <= 32, M, N, E <=
+ * 65535, that sum within 163840 bytes), 0 when it does not (lds_bytes is the
+ * same sum), or LDPC_EINVAL (ldpc_last_error(NULL)) for mb, nb or Z < 1, Z >
+ * 1024 or a shift outside [-1, Z).  (Replaces nothing in the reference, which
+ * has one dense 32x64 H, lib/ldpc_decoder_cb_impl.cc:60-102.) */
+int ldpc_plan_qc(int mb, int nb, int Z, const int32_t *shifts, int precision,
+                 int32_t *row_ptr_out_opt, int32_t *col_idx_out_opt, int64_t *lds_bytes_out_opt,
+                 int *threads_out_opt);
+
 /* ---- device context ----------------------------------------------- */
 
 /* Builds the decoder's view of H (reorderHMatrix unless
@@ -197,6 +225,16 @@ ldpc_ctx *ldpc_create(const uint8_t *H, int M, int N, int flags, int device);
  * it; larger ones (dc <= 32, dv <= 16) keep their messages in HBM. */
 ldpc_ctx *ldpc_create_csr(int M, int N, const int32_t *row_ptr, const int32_t *col_idx,
                           int flags, int device);
+/* The same from a quasi-cyclic base matrix (ldpc_plan_qc): the code is expanded
+ * and the context built exactly as ldpc_create_csr builds it for that CSR --
+ * the same flags (LDPC_FLAG_GRAPH, LDPC_FLAG_ONCHIP), limits and choice of
+ * path, every entry point working on it unchanged -- and the context remembers
+ * the base matrix (ldpc_ctx_qc).  Its layered decodes (ldpc_decode_layered*)
+ * take the block rows as their plan and, while that plan is in force, run the
+ * circulant kernel (csrc/ldpc_layered_qc.hip); with LDPC_FLAG_QC_TABLES they
+ * keep the plan and run the per-edge table kernel.  A code outside the layered
+ * kernels' limits still gets a context; its layered decodes alone are refused. */
+ldpc_ctx *ldpc_create_qc(int mb, int nb, int Z, const int32_t *shifts, int flags, int device);
 void ldpc_destroy(ldpc_ctx *ctx);
 const char *ldpc_last_error(const ldpc_ctx *ctx);
 
@@ -208,6 +246,10 @@ int ldpc_ctx_info(const ldpc_ctx *ctx, int *M, int *N, int *E, int *K, int *KB,
 int ldpc_ctx_h(const ldpc_ctx *ctx, uint8_t *H_out);
 /* Copies the context's H as CSR (row_ptr: M+1, col_idx: E); either may be NULL. */
 int ldpc_ctx_csr(const ldpc_ctx *ctx, int32_t *row_ptr_out, int32_t *col_idx_out);
+/* 1 for a context made by ldpc_create_qc, with its mb, nb, Z and base matrix
+ * (shifts_out: mb * nb ints; any pointer may be NULL); 0 for any other (mb, nb
+ * and Z are then 0). */
+int ldpc_ctx_qc(const ldpc_ctx *ctx, int *mb, int *nb, int *Z, int32_t *shifts_out_opt);
 /* 0: small-code kernel (frame per wave / workgroup, registers + LDS);
  * 1: large-code kernels (messages in HBM);
  * 2: on-chip kernels (LDPC_FLAG_ONCHIP: frame per workgroup, messages in LDS;
@@ -373,12 +415,17 @@ int ldpc_decode_device(ldpc_ctx *ctx, int method, int max_iters,
  *
  *   ldpc_ctx_layers     the plan in force: copies the layer of every row (M
  *                       ints, optional) and returns L.  The planner's
- *                       (ldpc_plan_layers) until ldpc_set_layers replaces it.
+ *                       (ldpc_plan_layers; on a quasi-cyclic context the
+ *                       block rows, layer_of_row[j] = j / Z) until
+ *                       ldpc_set_layers replaces it.
  *   ldpc_set_layers     a caller's plan, e.g. the block rows of a QC code:
  *                       layer_of_row (M) in [0, M), no column twice in a layer;
  *                       otherwise LDPC_EINVAL, the message naming the two rows
  *                       and the column, and the plan in force stays.  NULL
- *                       restores the planner's.
+ *                       restores the planner's.  On a quasi-cyclic context
+ *                       decodes run the circulant kernel while the plan in
+ *                       force is the block rows and the table kernel under any
+ *                       other; the results are the contract's either way.
  *   ldpc_decode_layered          host buffers, synchronous; parameters as
  *                       ldpc_decode_strided with `scale` in place of `method`.
  *   ldpc_decode_layered_device   device buffers, enqueued on hip_stream;
