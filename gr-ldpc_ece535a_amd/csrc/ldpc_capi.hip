@@ -6,6 +6,7 @@
 // when no device is usable ldpc_create fails with LDPC_EDEVICE.
 #include <hip/hip_runtime.h>
 
+#include <float.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -27,6 +28,7 @@
 #include "ldpc_kernels.hpp"
 #include "ldpc_layout.hpp"
 #include "ldpc_layered.hpp"
+#include "ldpc_layered_q8.hpp"
 #include "ldpc_qc.hpp"
 #include "ldpc_onchip.hpp"
 
@@ -212,7 +214,8 @@ struct ldpc_ctx {
   // changed
   std::vector<int32_t> lay_of_row;
   int lay_L = 0;            // 0: no plan yet
-  bool lay_ready = false;   // the device tables are those of lay_of_row
+  bool lay_ready = false;   // lay_f64 / lay_f32 are those of lay_of_row, and the code fits float
+  bool lay_tabs = false;    // the device tables are those of lay_of_row (float and q8 decodes share them)
   ldpc::LayeredLayout lay_f64{}, lay_f32{};
   uint32_t *d_lay_rows = nullptr, *d_lay_off = nullptr;
   uint16_t *d_lay_ci = nullptr, *d_lay_order = nullptr;
@@ -227,6 +230,11 @@ struct ldpc_ctx {
   bool lay_qc = false;      // the tables uploaded are the circulant kernel's
   uint32_t *d_qc_rows = nullptr, *d_qc_ent = nullptr;
   int qc_rows = 0;          // block rows in d_qc_rows (those with an entry)
+  // fixed-point layered min-sum (ldpc_layered_q8.hip, ldpc_decode_layered_q8*):
+  // the same plan and device tables, a layout and limits of its own
+  bool q8_ready = false;    // lay_q8 is that of lay_of_row, and the code fits
+  ldpc::LayeredLayout lay_q8{};
+  int q8_resident = 0;      // workgroups the device holds of the kernel lay_q8 selects
   // device encoder (built on first ldpc_encode_device): 1 small (A = H_p^-1 H_d
   // bit rows in d_encA), 2 IRA staircase, -1 no systematic encoder
   int enc_kind = 0;
@@ -1531,6 +1539,10 @@ int largest_layer(const std::vector<int32_t> &layer_of_row, int L) {
   return most;
 }
 
+// A new plan is in force: the layouts and the device tables of the float and
+// the fixed-point decoder are the old plan's.
+void plan_changed(ldpc_ctx *ctx) { ctx->lay_ready = ctx->lay_tabs = ctx->q8_ready = false; }
+
 // The context's plan: the planner's -- on a quasi-cyclic context the block
 // rows -- unless the caller has set one.  Host only.
 void ensure_layer_plan(ldpc_ctx *ctx) {
@@ -1542,7 +1554,7 @@ void ensure_layer_plan(ldpc_ctx *ctx) {
   } else {
     ctx->lay_L = ldpc::plan_layers(ctx->M, ctx->N, ctx->rp.data(), ctx->ci.data(), ctx->lay_of_row);
   }
-  ctx->lay_ready = false;
+  plan_changed(ctx);
 }
 
 // The plan in force is the block rows of a quasi-cyclic context, whoever set it.
@@ -1553,39 +1565,22 @@ bool block_row_plan(const ldpc_ctx *ctx) {
   return true;
 }
 
-// Builds and uploads the layered decoder's tables from the context's CSR and
-// the plan in force (first use, or the first decode after ldpc_set_layers).
-int prepare_layered(ldpc_ctx *ctx) {
-  ensure_layer_plan(ctx);
-  if (ctx->lay_ready) return LDPC_OK;
-  const int most = largest_layer(ctx->lay_of_row, ctx->lay_L);
-  ldpc::layered_layout(ctx->M, ctx->N, ctx->E, ctx->dc_max, ctx->lay_L, most, 0, ctx->lay_f64);
-  const bool f32 = ldpc::layered_layout(ctx->M, ctx->N, ctx->E, ctx->dc_max, ctx->lay_L, most, 1,
-                                        ctx->lay_f32);
-  if (!f32) {  // what no precision fits; a code that fits float alone is refused per decode
-    char buf[256];
-    snprintf(buf, sizeof buf,
-             "the code does not fit the layered kernels: a frame needs %d bytes of LDS in float "
-             "(%d in double), the limit is %d; M, N, E must be <= %d and check degrees <= %d "
-             "(M=%d N=%d E=%d dc_max=%d)",
-             ctx->lay_f32.frame, ctx->lay_f64.frame, ldpc::kLayeredLdsLimit,
-             ldpc::kLayeredIndexMax, ldpc::kLayeredDcMax, ctx->M, ctx->N, ctx->E, ctx->dc_max);
-    return set_err(ctx, LDPC_EUNSUPPORTED, buf);
-  }
-  // the circulant kernel while the block rows of a quasi-cyclic context are
-  // the plan; the per-edge tables for any other plan and under LDPC_FLAG_QC_TABLES
-  const bool qc = !ctx->qc_tables && block_row_plan(ctx);
+// The circulant kernels while the block rows of a quasi-cyclic context are the
+// plan; the per-edge tables for any other plan and under LDPC_FLAG_QC_TABLES.
+bool circulant_route(const ldpc_ctx *ctx) { return !ctx->qc_tables && block_row_plan(ctx); }
+
+// Builds and uploads the tables of the plan in force (first use, or the first
+// decode after ldpc_set_layers), for the float and the fixed-point decoder
+// alike: the caller has checked that its decoder takes the code on this route.
+int upload_layered_tables(ldpc_ctx *ctx) {
+  if (ctx->lay_tabs) return LDPC_OK;
+  const bool qc = circulant_route(ctx);
   ldpc::LayeredTables t;
   ldpc::QcTables qt;
-  if (qc) {
+  if (qc)
     ldpc::qc_build(ctx->qc_mb, ctx->qc_nb, ctx->qc_Z, ctx->qc_shifts.data(), qt);
-    for (ldpc::LayeredLayout *lay : {&ctx->lay_f64, &ctx->lay_f32}) {
-      lay->staged = 0;  // the base tables are read through the scalar cache
-      lay->total = lay->frame;
-    }
-  } else {
+  else
     ldpc::layered_build(ctx->M, ctx->rp.data(), ctx->ci.data(), ctx->lay_of_row, ctx->lay_L, t);
-  }
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
   // decodes that read the previous plan's tables may still run (any stream)
@@ -1616,10 +1611,75 @@ int prepare_layered(ldpc_ctx *ctx) {
     upload(ctx, &ctx->d_tickets, zeros, "upload(tickets)", what, e);
   }
   if (what) return hip_err(ctx, e, what);
-  ctx->lay_resident[0] = ctx->lay_resident[1] = 0;  // the kernel, its threads and bytes may differ
   ctx->lay_qc = qc;
   ctx->qc_rows = (int)qt.rows.size();
+  ctx->lay_tabs = true;
+  return LDPC_OK;
+}
+
+// The float decoder's layouts for the plan in force, and the tables.
+int prepare_layered(ldpc_ctx *ctx) {
+  ensure_layer_plan(ctx);
+  if (ctx->lay_ready) return LDPC_OK;
+  const int most = largest_layer(ctx->lay_of_row, ctx->lay_L);
+  ldpc::layered_layout(ctx->M, ctx->N, ctx->E, ctx->dc_max, ctx->lay_L, most, 0, ctx->lay_f64);
+  const bool f32 = ldpc::layered_layout(ctx->M, ctx->N, ctx->E, ctx->dc_max, ctx->lay_L, most, 1,
+                                        ctx->lay_f32);
+  if (!f32) {  // what no precision fits; a code that fits float alone is refused per decode
+    char buf[256];
+    snprintf(buf, sizeof buf,
+             "the code does not fit the layered kernels: a frame needs %d bytes of LDS in float "
+             "(%d in double), the limit is %d; M, N, E must be <= %d and check degrees <= %d "
+             "(M=%d N=%d E=%d dc_max=%d)",
+             ctx->lay_f32.frame, ctx->lay_f64.frame, ldpc::kLayeredLdsLimit,
+             ldpc::kLayeredIndexMax, ldpc::kLayeredDcMax, ctx->M, ctx->N, ctx->E, ctx->dc_max);
+    return set_err(ctx, LDPC_EUNSUPPORTED, buf);
+  }
+  if (circulant_route(ctx))
+    for (ldpc::LayeredLayout *lay : {&ctx->lay_f64, &ctx->lay_f32}) {
+      lay->staged = 0;  // the base tables are read through the scalar cache
+      lay->total = lay->frame;
+    }
+  const int rc = upload_layered_tables(ctx);
+  if (rc != LDPC_OK) return rc;
+  ctx->lay_resident[0] = ctx->lay_resident[1] = 0;  // the kernel, its threads and bytes may differ
   ctx->lay_ready = true;
+  return LDPC_OK;
+}
+
+// The fixed-point decoder's layout for the plan in force, and the tables.
+int prepare_layered_q8(ldpc_ctx *ctx) {
+  ensure_layer_plan(ctx);
+  if (ctx->q8_ready) return LDPC_OK;
+  const bool qc = circulant_route(ctx);
+  const bool fits = ldpc::layered_q8_layout(
+      ctx->M, ctx->N, ctx->E, ctx->dc_max, ctx->dv_max, ctx->lay_L,
+      largest_layer(ctx->lay_of_row, ctx->lay_L), qc ? ctx->qc_Z : 0, ctx->lay_q8);
+  if (!fits) {
+    char buf[320];
+    if (qc)
+      snprintf(buf, sizeof buf,
+               "the code does not fit the fixed-point layered kernel: a frame needs %d bytes of "
+               "LDS, the limit is %d; M, N and the base entries must be <= %d, check degrees <= %d "
+               "and bit degrees <= %d (M=%d N=%d E=%d dc_max=%d dv_max=%d)",
+               ctx->lay_q8.frame, ldpc::kLayeredLdsLimit, ldpc::kLayeredIndexMax,
+               ldpc::kLayeredDcMax, ldpc::kLayeredQ8DvMax, ctx->M, ctx->N, ctx->E, ctx->dc_max,
+               ctx->dv_max);
+    else
+      snprintf(buf, sizeof buf,
+               "the code does not fit the fixed-point layered kernel on its per-edge tables: a "
+               "frame needs %d bytes of LDS, the limit is %d; M, N, E must be <= %d (only the "
+               "circulant kernel of a quasi-cyclic context takes E beyond it), check degrees <= %d "
+               "and bit degrees <= %d (M=%d N=%d E=%d dc_max=%d dv_max=%d)",
+               ctx->lay_q8.frame, ldpc::kLayeredLdsLimit, ldpc::kLayeredIndexMax,
+               ldpc::kLayeredDcMax, ldpc::kLayeredQ8DvMax, ctx->M, ctx->N, ctx->E, ctx->dc_max,
+               ctx->dv_max);
+    return set_err(ctx, LDPC_EUNSUPPORTED, buf);
+  }
+  const int rc = upload_layered_tables(ctx);
+  if (rc != LDPC_OK) return rc;
+  ctx->q8_resident = 0;
+  ctx->q8_ready = true;
   return LDPC_OK;
 }
 
@@ -1646,21 +1706,40 @@ int layered_ready(ldpc_ctx *ctx, double scale, int precision) {
   return LDPC_OK;
 }
 
+// The fixed-point decoder's parameters (ldpc_decode_layered_q8*).
+struct Q8Params {
+  int num;
+  float llr_scale;
+};
+
+// The same for a fixed-point layered decode: no ring session, num in [1, 16]
+// and a finite llr_scale > 0, then a code that fits on the route in force.
+int layered_q8_ready(ldpc_ctx *ctx, const Q8Params &q8) {
+  if (ctx->ring_on)
+    return set_err(ctx, LDPC_EINVAL, "a frame ring session is open (ldpc_ring_end)");
+  if (q8.num < 1 || q8.num > 16) return set_err(ctx, LDPC_EINVAL, "num must be in [1, 16]");
+  if (!(q8.llr_scale > 0.0f && q8.llr_scale <= FLT_MAX))
+    return set_err(ctx, LDPC_EINVAL, "llr_scale must be finite and > 0");
+  return prepare_layered_q8(ctx);
+}
+
 // Enqueues one layered decode of device-resident frames (decode_device_impl
-// for the layered kernel: same inputs, outputs and frame queues).
+// for the layered kernel: same inputs, outputs and frame queues).  q8: the
+// decode is the fixed-point decoder's (scale and precision unused).
 int layered_device_impl(ldpc_ctx *ctx, double scale, int max_iters, int et_period, int precision,
                         const float *d_in, int64_t cw_stride, int elem_stride, float polarity,
                         int B, uint8_t *d_out_packed, uint8_t *d_out_bits_opt,
                         int32_t *d_iters_used_opt, int32_t *d_syn_weight_opt,
-                        float *d_llr_out_opt, void *hip_stream) {
+                        float *d_llr_out_opt, void *hip_stream, const Q8Params *q8 = nullptr) {
   serve_stop(ctx);
   int method = LDPC_METHOD_LOGDOMAIN;
   int rc = check_decode_args(ctx, method, max_iters, et_period, precision, B, elem_stride,
                              cw_stride);
   if (rc != LDPC_OK) return rc;
-  if ((rc = layered_ready(ctx, scale, precision)) != LDPC_OK) return rc;
+  if ((rc = q8 ? layered_q8_ready(ctx, *q8) : layered_ready(ctx, scale, precision)) != LDPC_OK)
+    return rc;
   const int f32 = precision == LDPC_PREC_F32 ? 1 : 0;
-  const ldpc::LayeredLayout &lay = f32 ? ctx->lay_f32 : ctx->lay_f64;
+  const ldpc::LayeredLayout &lay = q8 ? ctx->lay_q8 : f32 ? ctx->lay_f32 : ctx->lay_f64;
   if (B == 0) return LDPC_OK;
   if (!d_in || !d_out_packed) return set_err(ctx, LDPC_EINVAL, "null device buffer");
   ldpc::DecodeArgs a{};
@@ -1699,8 +1778,10 @@ int layered_device_impl(ldpc_ctx *ctx, double scale, int max_iters, int et_perio
     v.KB = ctx->KB;
     v.mb = ctx->qc_rows;
     v.Z = ctx->qc_Z;
-    launched = ldpc::launch_layered_qc_decode(v, a, lay, scale, f32, st, ctx->lay_resident,
-                                              &advance);
+    launched = q8 ? ldpc::launch_layered_q8_qc_decode(v, a, lay, q8->num, q8->llr_scale, st,
+                                                      &ctx->q8_resident, &advance)
+                  : ldpc::launch_layered_qc_decode(v, a, lay, scale, f32, st, ctx->lay_resident,
+                                                   &advance);
   } else {
     ldpc::LayeredView v;
     v.rows = ctx->d_lay_rows;
@@ -1712,7 +1793,10 @@ int layered_device_impl(ldpc_ctx *ctx, double scale, int max_iters, int et_perio
     v.E = ctx->E;
     v.KB = ctx->KB;
     v.L = ctx->lay_L;
-    launched = ldpc::launch_layered_decode(v, a, lay, scale, f32, st, ctx->lay_resident, &advance);
+    launched = q8 ? ldpc::launch_layered_q8_decode(v, a, lay, q8->num, q8->llr_scale, st,
+                                                   &ctx->q8_resident, &advance)
+                  : ldpc::launch_layered_decode(v, a, lay, scale, f32, st, ctx->lay_resident,
+                                                &advance);
   }
   if (launched != 0) return hip_err(ctx, hipGetLastError(), "kernel launch");
   ctx->queues[q].base += advance;
@@ -1723,12 +1807,13 @@ int layered_device_impl(ldpc_ctx *ctx, double scale, int max_iters, int et_perio
 // polarities).  The frames' samples are staged through a pinned buffer; for
 // an interleaved gr_complex stream (elem_stride 2, even cw_stride) only the
 // real parts are gathered and copied, and the kernel reads them densely.
-// layered_scale: the decode is ldpc_decode_layered's (method unused).
+// layered_scale: the decode is ldpc_decode_layered's (method unused); q8: it
+// is ldpc_decode_layered_q8's (method and precision unused).
 int decode_host_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, int precision,
                      const float *in, int64_t n_in_floats, int64_t cw_stride, int elem_stride,
                      float polarity, int B, bool both, uint8_t *out_packed, uint8_t *out_bits_opt,
                      int32_t *iters_used_opt, int32_t *syn_weight_opt, float *llr_out_opt,
-                     const double *layered_scale = nullptr) {
+                     const double *layered_scale = nullptr, const Q8Params *q8 = nullptr) {
   serve_stop(ctx);
   int rc = check_decode_args(ctx, method, max_iters, et_period, precision, B, elem_stride,
                              cw_stride);
@@ -1736,6 +1821,7 @@ int decode_host_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, in
   // a layered decode that will be refused is refused before anything is staged
   if (layered_scale && (rc = layered_ready(ctx, *layered_scale, precision)) != LDPC_OK)
     return rc;
+  if (q8 && (rc = layered_q8_ready(ctx, *q8)) != LDPC_OK) return rc;
   if (B == 0) return LDPC_OK;
   if (!in || !out_packed) return set_err(ctx, LDPC_EINVAL, "null buffer");
   const int64_t span = (int64_t)(B - 1) * cw_stride + (int64_t)(ctx->N - 1) * elem_stride + 1;
@@ -1775,9 +1861,10 @@ int decode_host_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, in
   if ((e = hipMemcpyAsync(d_in, h, (size_t)n_stage * 4, hipMemcpyHostToDevice, ctx->stream)) !=
       hipSuccess)
     return hip_err(ctx, e, "hipMemcpyAsync(in)");
-  if (layered_scale)
-    rc = layered_device_impl(ctx, *layered_scale, max_iters, et_period, precision, d_in, cw, es,
-                             polarity, BO, d_pk, d_bits, d_it, d_sy, d_llr, ctx->stream);
+  if (layered_scale || q8)
+    rc = layered_device_impl(ctx, layered_scale ? *layered_scale : 1.0, max_iters, et_period,
+                             precision, d_in, cw, es, polarity, BO, d_pk, d_bits, d_it, d_sy,
+                             d_llr, ctx->stream, q8);
   else
     rc = decode_device_impl(ctx, method, max_iters, et_period, precision, d_in, cw, es, polarity,
                             BO, both ? B : 0, d_pk, d_bits, d_it, d_sy, d_llr, ctx->stream);
@@ -2691,7 +2778,7 @@ int ldpc_set_layers(ldpc_ctx *ctx, const int32_t *layer_of_row) {
   if (L < 0) return set_err(ctx, LDPC_EINVAL, "bad layer plan: " + why);
   ctx->lay_of_row.assign(layer_of_row, layer_of_row + ctx->M);
   ctx->lay_L = L;
-  ctx->lay_ready = false;
+  plan_changed(ctx);
   return LDPC_OK;
 }
 
@@ -2752,6 +2839,84 @@ int ldpc_decode_layered_device(ldpc_ctx *ctx, double scale, int max_iters, int e
   return layered_device_impl(ctx, scale, max_iters, et_period, precision, d_in, cw_stride,
                              elem_stride, polarity, B, d_out_packed, d_out_bits_opt,
                              d_iters_used_opt, d_syn_weight_opt, d_llr_out_opt, hip_stream);
+}
+
+// The column degrees of a CSR H: the largest.
+static int csr_dv_max(int N, int E, const int32_t *ci) {
+  std::vector<int32_t> dv((size_t)N, 0);
+  int most = 0;
+  for (int e = 0; e < E; ++e) most = std::max(most, ++dv[ci[e]]);
+  return most;
+}
+
+int ldpc_plan_layers_q8(int M, int N, const int32_t *row_ptr, const int32_t *col_idx,
+                        int32_t *layer_of_row_out_opt, int *n_layers_out_opt,
+                        int64_t *lds_bytes_out_opt, int *threads_out_opt) {
+  g_create_error.clear();
+  if (!valid_csr(M, N, row_ptr, col_idx))
+    return set_err(nullptr, LDPC_EINVAL, "CSR H must be M x N (M < N), columns ascending and in range");
+  try {
+    std::vector<int32_t> plan;
+    const int L = ldpc::plan_layers(M, N, row_ptr, col_idx, plan);
+    int dc_max = 0;
+    for (int j = 0; j < M; ++j) dc_max = std::max(dc_max, row_ptr[j + 1] - row_ptr[j]);
+    ldpc::LayeredLayout lay;
+    const bool fits = ldpc::layered_q8_layout(M, N, row_ptr[M], dc_max,
+                                              csr_dv_max(N, row_ptr[M], col_idx), L,
+                                              largest_layer(plan, L), 0, lay);
+    if (layer_of_row_out_opt) std::copy(plan.begin(), plan.end(), layer_of_row_out_opt);
+    if (n_layers_out_opt) *n_layers_out_opt = L;
+    if (lds_bytes_out_opt) *lds_bytes_out_opt = fits ? lay.total : lay.frame;
+    if (threads_out_opt) *threads_out_opt = lay.threads;
+    return fits ? 1 : 0;
+  } catch (const std::exception &e) {
+    return set_err(nullptr, LDPC_ENOMEM, e.what());
+  }
+}
+
+int ldpc_plan_qc_q8(int mb, int nb, int Z, const int32_t *shifts, int64_t *lds_bytes_out_opt,
+                    int *threads_out_opt) {
+  g_create_error.clear();
+  std::string why;
+  if (!ldpc::qc_check(mb, nb, Z, shifts, &why))
+    return set_err(nullptr, LDPC_EINVAL, "bad quasi-cyclic code: " + why);
+  int entries, row_max, col_max = 0;
+  ldpc::qc_count(mb, nb, shifts, entries, row_max);
+  for (int c = 0; c < nb; ++c) {
+    int d = 0;
+    for (int r = 0; r < mb; ++r) d += shifts[(size_t)r * nb + c] >= 0;
+    col_max = std::max(col_max, d);
+  }
+  // the block rows as a plan: mb layers of Z rows; nothing staged behind the frame
+  ldpc::LayeredLayout lay;
+  const bool fits = ldpc::layered_q8_layout(mb * Z, nb * Z, (int64_t)entries * Z, row_max, col_max,
+                                            mb, Z, Z, lay);
+  if (lds_bytes_out_opt) *lds_bytes_out_opt = lay.frame;
+  if (threads_out_opt) *threads_out_opt = lay.threads;
+  return fits ? 1 : 0;
+}
+
+int ldpc_decode_layered_q8(ldpc_ctx *ctx, int num, float llr_scale, int max_iters, int et_period,
+                           const float *in, int64_t n_in_floats, int64_t cw_stride,
+                           int elem_stride, float polarity, int B, uint8_t *out_packed,
+                           uint8_t *out_bits_opt, int32_t *iters_used_opt,
+                           int32_t *syn_weight_opt, float *llr_out_opt) {
+  const Q8Params q8{num, llr_scale};
+  return decode_host_impl(ctx, LDPC_METHOD_LOGDOMAIN, max_iters, et_period, LDPC_PREC_F32, in,
+                          n_in_floats, cw_stride, elem_stride, polarity, B, false, out_packed,
+                          out_bits_opt, iters_used_opt, syn_weight_opt, llr_out_opt, nullptr, &q8);
+}
+
+int ldpc_decode_layered_q8_device(ldpc_ctx *ctx, int num, float llr_scale, int max_iters,
+                                  int et_period, const float *d_in, int64_t cw_stride,
+                                  int elem_stride, float polarity, int B, uint8_t *d_out_packed,
+                                  uint8_t *d_out_bits_opt, int32_t *d_iters_used_opt,
+                                  int32_t *d_syn_weight_opt, float *d_llr_out_opt,
+                                  void *hip_stream) {
+  const Q8Params q8{num, llr_scale};
+  return layered_device_impl(ctx, 1.0, max_iters, et_period, LDPC_PREC_F32, d_in, cw_stride,
+                             elem_stride, polarity, B, d_out_packed, d_out_bits_opt,
+                             d_iters_used_opt, d_syn_weight_opt, d_llr_out_opt, hip_stream, &q8);
 }
 
 int ldpc_ctx_streams(ldpc_ctx *ctx, int n, void **streams_out) {

@@ -101,6 +101,32 @@ bool layered_layout(int M, int N, int E, int dc_max, int L, int max_layer_rows, 
   return fits;
 }
 
+bool layered_q8_layout(int M, int N, int64_t E, int dc_max, int dv_max, int L,
+                       int max_layer_rows, int Z, LayeredLayout &lay) {
+  const bool tables = Z <= 0;
+  const int64_t r = al16((int64_t)N * 2), red = r + al16(E), frame = red + kRedBytes;
+  const int64_t threads = std::min<int64_t>(
+      kLayeredMaxThreads, std::max<int64_t>(64, ((int64_t)max_layer_rows + 63) / 64 * 64));
+  const bool fits = frame <= kLayeredLdsLimit && M <= kLayeredIndexMax && N <= kLayeredIndexMax &&
+                    (tables ? E : E / Z) <= kLayeredIndexMax && dc_max <= kLayeredDcMax &&
+                    dv_max <= kLayeredQ8DvMax;
+  const int64_t rows = frame, ci = rows + al16((int64_t)M * 4), order = ci + al16(E * 2);
+  const int64_t off = order + al16((int64_t)M * 2), staged_total = off + al16(((int64_t)L + 1) * 4);
+  const bool staged = tables && fits && staged_total <= kLayeredLdsLimit;
+  const int64_t cap = 0x7fffffff;
+  lay.r = (int)std::min(r, cap);
+  lay.hard = lay.red = (int)std::min(red, cap);
+  lay.rows = (int)std::min(rows, cap);
+  lay.ci = (int)std::min(ci, cap);
+  lay.order = (int)std::min(order, cap);
+  lay.off = (int)std::min(off, cap);
+  lay.staged = staged ? 1 : 0;
+  lay.frame = (int)std::min(frame, cap);
+  lay.total = (int)std::min(staged ? staged_total : frame, cap);
+  lay.threads = (int)threads;
+  return fits;
+}
+
 void layered_build(int M, const int32_t *rp, const int32_t *ci,
                    const std::vector<int32_t> &layer_of_row, int L, LayeredTables &t) {
   const int E = rp[M];

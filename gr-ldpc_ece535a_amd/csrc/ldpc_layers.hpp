@@ -56,6 +56,22 @@ struct LayeredLayout {
 bool layered_layout(int M, int N, int E, int dc_max, int L, int max_layer_rows, int prec,
                     LayeredLayout &lay);
 
+// The fixed-point decoder's layout (ldpc_layered_q8.hip): LQ int16[N] at
+// offset 0, R int8[E] at `r`, the reduction words at `red` (`hard` is unused
+// and equals `red`: the decisions are LQ < 0, read in place), every term
+// rounded up to 16 bytes:
+//   frame = a16(2 N) + a16(E) + 128
+// Z == 0: the per-edge table route, whose 16-bit fields need E <=
+// kLayeredIndexMax and whose tables are staged behind the frame where they
+// fit; Z > 0: the circulant route at that lifting size, which stages nothing
+// and whose words bound the base entries, E / Z <= kLayeredIndexMax, and E by
+// the frame alone.  Either way M, N <= kLayeredIndexMax, dc_max <= kLayeredDcMax and
+// 127 (dv_max + 1) <= 32767: LQ[c] = Lc_c + the sum of the column's R after
+// every update, so |LQ| <= 127 (dv + 1) and int16 is exact without saturation.
+constexpr int kLayeredQ8DvMax = 32767 / 127 - 1;
+bool layered_q8_layout(int M, int N, int64_t E, int dc_max, int dv_max, int L,
+                       int max_layer_rows, int Z, LayeredLayout &lay);
+
 struct LayeredTables {
   std::vector<uint32_t> rows;   // M: first edge | degree << 16
   std::vector<uint16_t> ci;     // E: column of CSR edge e

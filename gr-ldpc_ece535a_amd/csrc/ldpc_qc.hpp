@@ -38,8 +38,10 @@ void qc_expand(int mb, int nb, int Z, const int32_t *shifts, std::vector<int32_t
 //                                  rows without any are left out (nothing to
 //                                  update, always satisfied), so every d_r >= 1
 //   ent[eb_r + k] = c_k * Z | s_k << 16   the row's entries in ascending c_k
-// (a code that fits the layered kernels has N, E <= 65535, so c * Z and the
-// number of entries fit 16 bits, and s < Z <= 1024).  ent ends with kQcEntPad zero words, so that the kernel
+// (a code that fits the layered kernels has N <= 65535 and at most 65535 base
+// entries -- the float kernels through E <= 65535, the fixed-point one through
+// layered_q8_layout's E / Z <= 65535 -- so c * Z and the number of entries fit
+// 16 bits, and s < Z <= 1024).  ent ends with kQcEntPad zero words, so that the kernel
 // may load a whole register row (up to 16 words) from any eb_r without a bound: what lies past the row's degree is
 // another row's entries or zeros, either way a column of the code, and the
 // kernel reads it and drops the value.

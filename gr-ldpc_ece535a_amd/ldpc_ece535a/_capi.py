@@ -96,6 +96,12 @@ SIGNATURES = {
                                  ctypes.c_float, _i, _u8p, _u8p, _i32p, _i32p, _f32p]),
     "ldpc_decode_layered_device": (_i, [_vp, ctypes.c_double, _i, _i, _i, _vp, _i64, _i,
                                         ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldpc_plan_layers_q8": (_i, [_i, _i, _i32p, _i32p, _i32p, _i32p, _i64p, _i32p]),
+    "ldpc_plan_qc_q8": (_i, [_i, _i, _i, _i32p, _i64p, _i32p]),
+    "ldpc_decode_layered_q8": (_i, [_vp, _i, ctypes.c_float, _i, _i, _f32p, _i64, _i64, _i,
+                                    ctypes.c_float, _i, _u8p, _u8p, _i32p, _i32p, _f32p]),
+    "ldpc_decode_layered_q8_device": (_i, [_vp, _i, ctypes.c_float, _i, _i, _vp, _i64, _i,
+                                           ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
@@ -264,6 +270,33 @@ def plan_qc(base, Z, precision=PREC_F64):
                                      ctypes.byref(threads)))
     return dict(fits=bool(fits), lds_bytes=lds.value, threads=threads.value,
                 csr=(M, N, rp, ci[:E]))
+
+
+def plan_layers_q8(csr):
+    """ldpc_plan_layers_q8 (host only, no GPU): plan_layers for the fixed-point
+    layered decoder's table route -- the same plan, lds_bytes = a16(2 N) +
+    a16(E) + 128 plus the tables where they fit behind it."""
+    M, N, rp, ci = csr
+    rp = np.ascontiguousarray(rp, np.int32)
+    ci = np.ascontiguousarray(ci, np.int32)
+    plan = np.zeros(max(int(M), 1), np.int32)
+    L, lds, threads = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int32(0)
+    fits = _check(lib().ldpc_plan_layers_q8(int(M), int(N), _p(rp, _i32p), _p(ci, _i32p),
+                                            _p(plan, _i32p), ctypes.byref(L), ctypes.byref(lds),
+                                            ctypes.byref(threads)))
+    return dict(fits=bool(fits), layer_of_row=plan[:M], n_layers=L.value, lds_bytes=lds.value,
+                threads=threads.value)
+
+
+def plan_qc_q8(base, Z):
+    """ldpc_plan_qc_q8 (host only, no GPU): plan_qc for the fixed-point layered
+    decoder's circulant route, without the expansion: dict with fits, lds_bytes
+    (one frame: a16(2 N) + a16(E) + 128) and threads."""
+    base, Z = _qc_base(base, Z)
+    lds, threads = ctypes.c_int64(0), ctypes.c_int32(0)
+    fits = _check(lib().ldpc_plan_qc_q8(base.shape[0], base.shape[1], Z, _p(base, _i32p),
+                                        ctypes.byref(lds), ctypes.byref(threads)))
+    return dict(fits=bool(fits), lds_bytes=lds.value, threads=threads.value)
 
 
 class Decoder:
@@ -572,6 +605,48 @@ class Decoder:
                                                 int(cw_stride), int(elem_stride), float(polarity),
                                                 int(B), d_packed, d_bits, d_iters, d_synd, d_llr,
                                                 stream), self._ctx)
+
+    def decode_layered_q8(self, llr, num=16, llr_scale=8.0, max_iters=50, et_period=1,
+                          polarity=1.0, cw_stride=None, elem_stride=1, B=None, want_bits=True,
+                          want_llr=False):
+        """ldpc_decode_layered_q8: fixed-point layered normalized min-sum
+        (int8 messages, factor num / 16, samples scaled by llr_scale and
+        rounded into [-127, 127]) of host float32 frames (synchronous);
+        arguments and result as decode_layered()."""
+        x = np.ascontiguousarray(llr, np.float32).reshape(-1)
+        if cw_stride is None:
+            cw_stride = self.N * elem_stride
+        if B is None:
+            B = x.size // cw_stride if cw_stride else 0
+        packed = np.zeros((B, self.KB), np.uint8)
+        bits = np.zeros((B, self.N), np.uint8) if want_bits else None
+        iters = np.zeros(B, np.int32)
+        synd = np.zeros(B, np.int32)
+        post = np.zeros((B, self.N), np.float32) if want_llr else None
+        _check(lib().ldpc_decode_layered_q8(self._ctx, int(num), float(llr_scale), int(max_iters),
+                                            int(et_period), _p(x, _f32p), x.size, int(cw_stride),
+                                            int(elem_stride), float(polarity), int(B),
+                                            _p(packed, _u8p), _p(bits, _u8p), _p(iters, _i32p),
+                                            _p(synd, _i32p), _p(post, _f32p)), self._ctx)
+        out = dict(packed=packed, iters=iters, synd=synd)
+        if want_bits:
+            out["bits"] = bits
+        if want_llr:
+            out["llr"] = post
+        return out
+
+    def decode_layered_q8_device(self, d_in, B, d_packed, num=16, llr_scale=8.0, max_iters=50,
+                                 et_period=1, polarity=1.0, cw_stride=None, elem_stride=1,
+                                 d_bits=None, d_iters=None, d_synd=None, d_llr=None, stream=None):
+        """ldpc_decode_layered_q8_device: enqueue a fixed-point layered decode
+        of device-resident buffers, as decode_layered_device()."""
+        if cw_stride is None:
+            cw_stride = self.N * elem_stride
+        _check(lib().ldpc_decode_layered_q8_device(self._ctx, int(num), float(llr_scale),
+                                                   int(max_iters), int(et_period), d_in,
+                                                   int(cw_stride), int(elem_stride),
+                                                   float(polarity), int(B), d_packed, d_bits,
+                                                   d_iters, d_synd, d_llr, stream), self._ctx)
 
     def set_launch_mode(self, mode):
         """MODE_LATENCY (default: one decode at a time) or MODE_THROUGHPUT

@@ -20,12 +20,15 @@ private copies.
 
     python -m ldpc_ece535a.ber [--frames 30] [--iterations 5]
                                [--ebn0 -7:10:0.5] [--code default|dvbs2] [--json out]
-                               [--layered SCALE]
+                               [--layered SCALE] [--layered-q8 NUM[:LLR_SCALE]]
 
 --layered SCALE adds a fifth curve, "LayeredMinSum": the layered normalized
 min-sum decoder (ldpc_decode_layered_device) at that scale, same iteration
-cap.  It is not one of the reference's decoders; without the option the
-output is the reference program's four curves.
+cap.  --layered-q8 NUM[:LLR_SCALE] adds "LayeredMinSumQ8": its fixed-point
+variant (ldpc_decode_layered_q8_device) at factor NUM / 16, the samples scaled
+by LLR_SCALE (default 8) before they are rounded.  Neither is one of the
+reference's decoders; without the options the output is the reference
+program's four curves.
 """
 import argparse
 import json
@@ -40,6 +43,7 @@ DEFAULT_EBN0 = [-7.0 + 0.5 * i for i in range(35)]  # :540
 METHODS = (("BPSK", _capi.METHOD_HARD), ("BitFlip", _capi.METHOD_BITFLIP),
            ("LogDomainSimple", _capi.METHOD_LOGDOMAIN), ("SumProduct", _capi.METHOD_SUMPRODUCT))
 LAYERED = "LayeredMinSum"
+LAYERED_Q8 = "LayeredMinSumQ8"
 
 
 def sigma_of(ebn0_db):
@@ -48,9 +52,10 @@ def sigma_of(ebn0_db):
 
 
 def sweep(dec=None, ebn0=DEFAULT_EBN0, frames=30, iterations=5, seed=0, precision=0, device=0,
-          layered_scale=None):
+          layered_scale=None, layered_q8=None):
     """Returns {method name: {"ber": [...], "fer": [...]}} over `ebn0`; with
-    layered_scale also LAYERED, the layered min-sum decoder at that scale."""
+    layered_scale also LAYERED, the layered min-sum decoder at that scale; with
+    layered_q8 = (num, llr_scale) also LAYERED_Q8, the fixed-point one."""
     import torch
     if dec is None:
         dec = _capi.Decoder(device=device)
@@ -65,7 +70,8 @@ def sweep(dec=None, ebn0=DEFAULT_EBN0, frames=30, iterations=5, seed=0, precisio
     d_err = torch.empty(B, dtype=torch.int32, device=dev)
     stream = torch.cuda.Stream(dev)
     sp = stream.cuda_stream
-    runs = list(METHODS) + ([(LAYERED, None)] if layered_scale is not None else [])
+    runs = (list(METHODS) + ([(LAYERED, None)] if layered_scale is not None else []) +
+            ([(LAYERED_Q8, None)] if layered_q8 is not None else []))
     out = {name: {"ber": [], "fer": []} for name, _ in runs}
     for i, db in enumerate(ebn0):
         s0 = (int(seed) * 1000003 + i) & 0xFFFFFFFF
@@ -76,7 +82,11 @@ def sweep(dec=None, ebn0=DEFAULT_EBN0, frames=30, iterations=5, seed=0, precisio
         for name, m in runs:
             kw = dict(max_iters=iterations, precision=precision, d_bits=d_bits.data_ptr(),
                       d_synd=d_synd.data_ptr(), stream=sp)
-            if m is None:
+            if name == LAYERED_Q8:
+                del kw["precision"]
+                dec.decode_layered_q8_device(d_tx.data_ptr(), B, d_packed.data_ptr(),
+                                             num=layered_q8[0], llr_scale=layered_q8[1], **kw)
+            elif m is None:
                 dec.decode_layered_device(d_tx.data_ptr(), B, d_packed.data_ptr(),
                                           scale=layered_scale, **kw)
             else:
@@ -94,8 +104,8 @@ def octave(ebn0, res):
     """The reference program's Octave output (apps/ldpc_lapack.cpp:707-811)."""
     f = lambda v: "%.4g" % v  # noqa: E731  (std::cout.precision(4))
     lines = ["EbN0=[" + " ".join(f(x) for x in ebn0) + " ];", "figure(1);"]
-    styles = ["'or--'", "'og-'", "'ob-'", "'om-'", "'ok-'"]
-    names = [name for name, _ in METHODS] + ([LAYERED] if LAYERED in res else [])
+    styles = ["'or--'", "'og-'", "'ob-'", "'om-'", "'ok-'", "'oc-'"]
+    names = [name for name, _ in METHODS] + [n for n in (LAYERED, LAYERED_Q8) if n in res]
     legend = "legend(" + ", ".join("'%s'" % n for n in names) + ");"
     for k, name in enumerate(names):
         lines.append("ber%d=[" % k + " ".join(f(x) for x in res[name]["ber"]) + " ];")
@@ -104,7 +114,7 @@ def octave(ebn0, res):
             lines.append("hold;")
     lines += ["grid on;", "hold off;", "title('Bit Error Rate');",
               legend, "xlabel('EbN0');", "ylabel('BER');", "figure(2);"]
-    fstyles = ["'or:'", "'og-'", "'ob-'", "'om-'", "'ok-'"]
+    fstyles = ["'or:'", "'og-'", "'ob-'", "'om-'", "'ok-'", "'oc-'"]
     for k, name in enumerate(names):
         lines.append("fer%d=[" % k)
         lines.append(", ".join(str(x) for x in res[name]["fer"]))  # printVector, :71-81
@@ -137,7 +147,14 @@ def main(argv=None):
     ap.add_argument("--json", default=None)
     ap.add_argument("--layered", type=float, default=None, metavar="SCALE",
                     help="add the layered normalized min-sum decoder at this scale (0 < SCALE <= 1)")
+    ap.add_argument("--layered-q8", default=None, metavar="NUM[:LLR_SCALE]",
+                    help="add the fixed-point layered min-sum decoder at factor NUM / 16 "
+                         "(NUM in 1..16), samples scaled by LLR_SCALE (default 8)")
     a = ap.parse_args(argv)
+    q8 = None
+    if a.layered_q8 is not None:
+        num, _, sc = a.layered_q8.partition(":")
+        q8 = (int(num), float(sc) if sc else 8.0)
     # torch first: it then shares its HIP runtime with libldpc_hip.so (see
     # INTEGRATION.md, "One HIP runtime per process")
     import torch  # noqa: F401
@@ -147,7 +164,8 @@ def main(argv=None):
     else:
         dec = _capi.Decoder()
     grid = parse_range(a.ebn0)
-    res = sweep(dec, grid, a.frames, a.iterations, a.seed, a.precision, layered_scale=a.layered)
+    res = sweep(dec, grid, a.frames, a.iterations, a.seed, a.precision, layered_scale=a.layered,
+                layered_q8=q8)
     sys.stdout.write(octave(grid, res))
     if a.json:
         json.dump({"ebn0": grid, "frames": a.frames, "iterations": a.iterations,

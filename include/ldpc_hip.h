@@ -449,6 +449,77 @@ int ldpc_decode_layered_device(ldpc_ctx *ctx, double scale, int max_iters, int e
                                int32_t *d_syn_weight_opt, float *d_llr_out_opt,
                                void *hip_stream);
 
+/* Fixed-point layered normalized min-sum ("q8"): an opt-in variant of the
+ * layered decoder above with int8 check messages R and int16 posteriors LQ in
+ * LDS, so that a frame takes a16(2 N) + a16(E) + 128 bytes (a16: rounded up to
+ * 16) where the float decoder takes 5 N + 4 E: codes about four times larger
+ * stay on chip.  Schedule, plan (ldpc_ctx_layers / ldpc_set_layers, shared
+ * with the float decoder, as are the device tables), exit rule, outputs and
+ * frame queue are the float decoder's.  `num` is the normalisation numerator,
+ * an integer in [1, 16]: the factor is num / 16 (16 = plain min-sum, 13 =
+ * 0.8125).  `llr_scale` (finite, > 0) is what a sample is multiplied by before
+ * it is rounded.  Per frame
+ *   tx_i = in_i * polarity              float; negated as an operation of its own
+ *   v_i  = (-tx_i) * llr_scale          one float multiply
+ *   Lc_i = 0 if v_i is NaN, else clamp(rint(v_i), -127, 127)
+ *                                       rint: ties to even; +-inf -> +-127
+ *   LQ[i] = Lc_i;  R[e] = 0
+ * then per iteration, for every layer in order and every row of it, with the
+ * row's edges e_k in ascending column c_k, in exact integer arithmetic:
+ *   q_k  = LQ[c_k] - R[e_k]
+ *   s_k  = q_k < 0 ? -1 : +1            sign(0) = +1: with the float decoder's
+ *                                       sign(0) = 0 a sample that quantises to 0
+ *                                       would zero its rows' messages for ever
+ *   P    = s_0 * ... * s_{d-1}
+ *   lo_k = min(127, min over t != k of |q_t|)      a row of degree 1: 127
+ *   R[e_k]  = (P * s_k) * ((lo_k * num + 8) >> 4)  rounded, not truncated;
+ *                                                  magnitude <= 127
+ *   LQ[c_k] = q_k + R[e_k]
+ * vhat_i = LQ[i] < 0; the cap first, then the syndrome on multiples of
+ * et_period; llr_out = (float)LQ.  LQ needs no saturation: LQ[c] = Lc_c + the
+ * sum of R over the column's rows holds exactly after every update, so |LQ| <=
+ * 127 * (dv + 1) -- at most 2159 for a context's dv <= 16 -- and int16 is
+ * exact (the limits below include 127 * (dv_max + 1) <= 32767).
+ *
+ * Limits: a frame within 163840 bytes, check degrees <= 32, M, N <= 65535.  On
+ * the per-edge table route (any context or plan; a quasi-cyclic context under
+ * LDPC_FLAG_QC_TABLES or a plan other than its block rows) also E <= 65535,
+ * and the tables are staged behind the frame where they fit.  On the circulant
+ * route (a quasi-cyclic context while the block rows are the plan) E is bound
+ * by the frame alone, and the base entries (E / Z) by 65535.
+ *
+ *   ldpc_plan_layers_q8   ldpc_plan_layers for this decoder's table route (no
+ *                         GPU): the same plan, lds_bytes_out the LDS a
+ *                         workgroup declares (the frame, plus the tables where
+ *                         they fit behind it; the frame alone when the code
+ *                         does not fit).  Returns 1 / 0 / a negative code alike.
+ *   ldpc_plan_qc_q8       ldpc_plan_qc for its circulant route (no GPU; no
+ *                         expansion is written): lds_bytes_out the frame.
+ *   ldpc_decode_layered_q8          parameters as ldpc_decode_layered with
+ *                         (num, llr_scale) in place of (scale, precision).
+ *   ldpc_decode_layered_q8_device   likewise, as ldpc_decode_layered_device.
+ * The decode calls refuse, in this order: an open frame ring session
+ * (LDPC_EINVAL); num outside [1, 16] or llr_scale not finite and > 0
+ * (LDPC_EINVAL); a code that does not fit on the route in force
+ * (LDPC_EUNSUPPORTED, the message naming the bytes a frame needs and the
+ * limits, on the table route the one on E). */
+int ldpc_plan_layers_q8(int M, int N, const int32_t *row_ptr, const int32_t *col_idx,
+                        int32_t *layer_of_row_out_opt, int *n_layers_out_opt,
+                        int64_t *lds_bytes_out_opt, int *threads_out_opt);
+int ldpc_plan_qc_q8(int mb, int nb, int Z, const int32_t *shifts, int64_t *lds_bytes_out_opt,
+                    int *threads_out_opt);
+int ldpc_decode_layered_q8(ldpc_ctx *ctx, int num, float llr_scale, int max_iters, int et_period,
+                           const float *in, int64_t n_in_floats, int64_t cw_stride,
+                           int elem_stride, float polarity, int B, uint8_t *out_packed,
+                           uint8_t *out_bits_opt, int32_t *iters_used_opt,
+                           int32_t *syn_weight_opt, float *llr_out_opt);
+int ldpc_decode_layered_q8_device(ldpc_ctx *ctx, int num, float llr_scale, int max_iters,
+                                  int et_period, const float *d_in, int64_t cw_stride,
+                                  int elem_stride, float polarity, int B, uint8_t *d_out_packed,
+                                  uint8_t *d_out_bits_opt, int32_t *d_iters_used_opt,
+                                  int32_t *d_syn_weight_opt, float *d_llr_out_opt,
+                                  void *hip_stream);
+
 /* The frame ring: ONE persistent launch decodes every batch posted to it
  * (small codes; min-sum and sum-product, any precision).  The frames of all
  * posted batches form one device queue, so a wave that finishes a frame of
