@@ -28,7 +28,6 @@
 #include "ldpc_kernels.hpp"
 #include "ldpc_layout.hpp"
 #include "ldpc_layered.hpp"
-#include "ldpc_layered_q8.hpp"
 #include "ldpc_qc.hpp"
 #include "ldpc_onchip.hpp"
 
@@ -223,14 +222,14 @@ struct ldpc_ctx {
   // a quasi-cyclic context (ldpc_create_qc) remembers its base matrix; its
   // planner's plan is the block rows, and while that plan is in force (and
   // LDPC_FLAG_QC_TABLES is not set) layered decodes run the circulant kernel
-  // (ldpc_layered_qc.hip) from the base tables d_qc_*
+  // (ldpc_layered.hip CirculantRoute) from the base tables d_qc_*
   int qc_mb = 0, qc_nb = 0, qc_Z = 0;  // qc_Z == 0: not a QC context
   std::vector<int32_t> qc_shifts;
   bool qc_tables = false;   // LDPC_FLAG_QC_TABLES
   bool lay_qc = false;      // the tables uploaded are the circulant kernel's
   uint32_t *d_qc_rows = nullptr, *d_qc_ent = nullptr;
   int qc_rows = 0;          // block rows in d_qc_rows (those with an entry)
-  // fixed-point layered min-sum (ldpc_layered_q8.hip, ldpc_decode_layered_q8*):
+  // fixed-point layered min-sum (ldpc_layered.hip Q8Arith, ldpc_decode_layered_q8*):
   // the same plan and device tables, a layout and limits of its own
   bool q8_ready = false;    // lay_q8 is that of lay_of_row, and the code fits
   ldpc::LayeredLayout lay_q8{};
@@ -1706,15 +1705,9 @@ int layered_ready(ldpc_ctx *ctx, double scale, int precision) {
   return LDPC_OK;
 }
 
-// The fixed-point decoder's parameters (ldpc_decode_layered_q8*).
-struct Q8Params {
-  int num;
-  float llr_scale;
-};
-
 // The same for a fixed-point layered decode: no ring session, num in [1, 16]
 // and a finite llr_scale > 0, then a code that fits on the route in force.
-int layered_q8_ready(ldpc_ctx *ctx, const Q8Params &q8) {
+int layered_q8_ready(ldpc_ctx *ctx, const ldpc::LayeredArith &q8) {
   if (ctx->ring_on)
     return set_err(ctx, LDPC_EINVAL, "a frame ring session is open (ldpc_ring_end)");
   if (q8.num < 1 || q8.num > 16) return set_err(ctx, LDPC_EINVAL, "num must be in [1, 16]");
@@ -1723,23 +1716,38 @@ int layered_q8_ready(ldpc_ctx *ctx, const Q8Params &q8) {
   return prepare_layered_q8(ctx);
 }
 
+// layered_ready or layered_q8_ready, as the arithmetic asks.
+int layered_arith_ready(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int precision) {
+  return ar.kind == ldpc::kLayeredQ8 ? layered_q8_ready(ctx, ar)
+                                     : layered_ready(ctx, ar.scale, precision);
+}
+
+// The arithmetic of ldpc_decode_layered* and of ldpc_decode_layered_q8*.
+ldpc::LayeredArith float_arith(double scale, int precision) {
+  return {precision == LDPC_PREC_F32 ? ldpc::kLayeredF32 : ldpc::kLayeredF64, scale, 0, 0.0f};
+}
+
+ldpc::LayeredArith q8_arith(int num, float llr_scale) {
+  return {ldpc::kLayeredQ8, 1.0, num, llr_scale};
+}
+
 // Enqueues one layered decode of device-resident frames (decode_device_impl
-// for the layered kernel: same inputs, outputs and frame queues).  q8: the
-// decode is the fixed-point decoder's (scale and precision unused).
-int layered_device_impl(ldpc_ctx *ctx, double scale, int max_iters, int et_period, int precision,
-                        const float *d_in, int64_t cw_stride, int elem_stride, float polarity,
-                        int B, uint8_t *d_out_packed, uint8_t *d_out_bits_opt,
+// for the layered kernel: same inputs, outputs and frame queues) in the
+// arithmetic `ar` (the fixed-point decoder's: precision is LDPC_PREC_F32, unused).
+int layered_device_impl(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_iters, int et_period,
+                        int precision, const float *d_in, int64_t cw_stride, int elem_stride,
+                        float polarity, int B, uint8_t *d_out_packed, uint8_t *d_out_bits_opt,
                         int32_t *d_iters_used_opt, int32_t *d_syn_weight_opt,
-                        float *d_llr_out_opt, void *hip_stream, const Q8Params *q8 = nullptr) {
+                        float *d_llr_out_opt, void *hip_stream) {
   serve_stop(ctx);
   int method = LDPC_METHOD_LOGDOMAIN;
   int rc = check_decode_args(ctx, method, max_iters, et_period, precision, B, elem_stride,
                              cw_stride);
   if (rc != LDPC_OK) return rc;
-  if ((rc = q8 ? layered_q8_ready(ctx, *q8) : layered_ready(ctx, scale, precision)) != LDPC_OK)
-    return rc;
-  const int f32 = precision == LDPC_PREC_F32 ? 1 : 0;
+  if ((rc = layered_arith_ready(ctx, ar, precision)) != LDPC_OK) return rc;
+  const bool q8 = ar.kind == ldpc::kLayeredQ8, f32 = ar.kind == ldpc::kLayeredF32;
   const ldpc::LayeredLayout &lay = q8 ? ctx->lay_q8 : f32 ? ctx->lay_f32 : ctx->lay_f64;
+  int *resident = q8 ? &ctx->q8_resident : &ctx->lay_resident[f32];
   if (B == 0) return LDPC_OK;
   if (!d_in || !d_out_packed) return set_err(ctx, LDPC_EINVAL, "null device buffer");
   ldpc::DecodeArgs a{};
@@ -1778,10 +1786,7 @@ int layered_device_impl(ldpc_ctx *ctx, double scale, int max_iters, int et_perio
     v.KB = ctx->KB;
     v.mb = ctx->qc_rows;
     v.Z = ctx->qc_Z;
-    launched = q8 ? ldpc::launch_layered_q8_qc_decode(v, a, lay, q8->num, q8->llr_scale, st,
-                                                      &ctx->q8_resident, &advance)
-                  : ldpc::launch_layered_qc_decode(v, a, lay, scale, f32, st, ctx->lay_resident,
-                                                   &advance);
+    launched = ldpc::launch_layered_decode(v, a, lay, ar, st, resident, &advance);
   } else {
     ldpc::LayeredView v;
     v.rows = ctx->d_lay_rows;
@@ -1793,10 +1798,7 @@ int layered_device_impl(ldpc_ctx *ctx, double scale, int max_iters, int et_perio
     v.E = ctx->E;
     v.KB = ctx->KB;
     v.L = ctx->lay_L;
-    launched = q8 ? ldpc::launch_layered_q8_decode(v, a, lay, q8->num, q8->llr_scale, st,
-                                                   &ctx->q8_resident, &advance)
-                  : ldpc::launch_layered_decode(v, a, lay, scale, f32, st, ctx->lay_resident,
-                                                &advance);
+    launched = ldpc::launch_layered_decode(v, a, lay, ar, st, resident, &advance);
   }
   if (launched != 0) return hip_err(ctx, hipGetLastError(), "kernel launch");
   ctx->queues[q].base += advance;
@@ -1807,21 +1809,19 @@ int layered_device_impl(ldpc_ctx *ctx, double scale, int max_iters, int et_perio
 // polarities).  The frames' samples are staged through a pinned buffer; for
 // an interleaved gr_complex stream (elem_stride 2, even cw_stride) only the
 // real parts are gathered and copied, and the kernel reads them densely.
-// layered_scale: the decode is ldpc_decode_layered's (method unused); q8: it
-// is ldpc_decode_layered_q8's (method and precision unused).
+// layered: the decode is a layered one in that arithmetic (method unused, and
+// for the fixed-point decoder precision too).
 int decode_host_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, int precision,
                      const float *in, int64_t n_in_floats, int64_t cw_stride, int elem_stride,
                      float polarity, int B, bool both, uint8_t *out_packed, uint8_t *out_bits_opt,
                      int32_t *iters_used_opt, int32_t *syn_weight_opt, float *llr_out_opt,
-                     const double *layered_scale = nullptr, const Q8Params *q8 = nullptr) {
+                     const ldpc::LayeredArith *layered = nullptr) {
   serve_stop(ctx);
   int rc = check_decode_args(ctx, method, max_iters, et_period, precision, B, elem_stride,
                              cw_stride);
   if (rc != LDPC_OK) return rc;
   // a layered decode that will be refused is refused before anything is staged
-  if (layered_scale && (rc = layered_ready(ctx, *layered_scale, precision)) != LDPC_OK)
-    return rc;
-  if (q8 && (rc = layered_q8_ready(ctx, *q8)) != LDPC_OK) return rc;
+  if (layered && (rc = layered_arith_ready(ctx, *layered, precision)) != LDPC_OK) return rc;
   if (B == 0) return LDPC_OK;
   if (!in || !out_packed) return set_err(ctx, LDPC_EINVAL, "null buffer");
   const int64_t span = (int64_t)(B - 1) * cw_stride + (int64_t)(ctx->N - 1) * elem_stride + 1;
@@ -1861,10 +1861,9 @@ int decode_host_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, in
   if ((e = hipMemcpyAsync(d_in, h, (size_t)n_stage * 4, hipMemcpyHostToDevice, ctx->stream)) !=
       hipSuccess)
     return hip_err(ctx, e, "hipMemcpyAsync(in)");
-  if (layered_scale || q8)
-    rc = layered_device_impl(ctx, layered_scale ? *layered_scale : 1.0, max_iters, et_period,
-                             precision, d_in, cw, es, polarity, BO, d_pk, d_bits, d_it, d_sy,
-                             d_llr, ctx->stream, q8);
+  if (layered)
+    rc = layered_device_impl(ctx, *layered, max_iters, et_period, precision, d_in, cw, es,
+                             polarity, BO, d_pk, d_bits, d_it, d_sy, d_llr, ctx->stream);
   else
     rc = decode_device_impl(ctx, method, max_iters, et_period, precision, d_in, cw, es, polarity,
                             BO, both ? B : 0, d_pk, d_bits, d_it, d_sy, d_llr, ctx->stream);
@@ -2825,9 +2824,10 @@ int ldpc_decode_layered(ldpc_ctx *ctx, double scale, int max_iters, int et_perio
                         const float *in, int64_t n_in_floats, int64_t cw_stride, int elem_stride,
                         float polarity, int B, uint8_t *out_packed, uint8_t *out_bits_opt,
                         int32_t *iters_used_opt, int32_t *syn_weight_opt, float *llr_out_opt) {
+  const ldpc::LayeredArith ar = float_arith(scale, precision);
   return decode_host_impl(ctx, LDPC_METHOD_LOGDOMAIN, max_iters, et_period, precision, in,
                           n_in_floats, cw_stride, elem_stride, polarity, B, false, out_packed,
-                          out_bits_opt, iters_used_opt, syn_weight_opt, llr_out_opt, &scale);
+                          out_bits_opt, iters_used_opt, syn_weight_opt, llr_out_opt, &ar);
 }
 
 int ldpc_decode_layered_device(ldpc_ctx *ctx, double scale, int max_iters, int et_period,
@@ -2836,9 +2836,10 @@ int ldpc_decode_layered_device(ldpc_ctx *ctx, double scale, int max_iters, int e
                                uint8_t *d_out_bits_opt, int32_t *d_iters_used_opt,
                                int32_t *d_syn_weight_opt, float *d_llr_out_opt,
                                void *hip_stream) {
-  return layered_device_impl(ctx, scale, max_iters, et_period, precision, d_in, cw_stride,
-                             elem_stride, polarity, B, d_out_packed, d_out_bits_opt,
-                             d_iters_used_opt, d_syn_weight_opt, d_llr_out_opt, hip_stream);
+  return layered_device_impl(ctx, float_arith(scale, precision), max_iters, et_period, precision,
+                             d_in, cw_stride, elem_stride, polarity, B, d_out_packed,
+                             d_out_bits_opt, d_iters_used_opt, d_syn_weight_opt, d_llr_out_opt,
+                             hip_stream);
 }
 
 // The column degrees of a CSR H: the largest.
@@ -2901,10 +2902,10 @@ int ldpc_decode_layered_q8(ldpc_ctx *ctx, int num, float llr_scale, int max_iter
                            int elem_stride, float polarity, int B, uint8_t *out_packed,
                            uint8_t *out_bits_opt, int32_t *iters_used_opt,
                            int32_t *syn_weight_opt, float *llr_out_opt) {
-  const Q8Params q8{num, llr_scale};
+  const ldpc::LayeredArith ar = q8_arith(num, llr_scale);
   return decode_host_impl(ctx, LDPC_METHOD_LOGDOMAIN, max_iters, et_period, LDPC_PREC_F32, in,
                           n_in_floats, cw_stride, elem_stride, polarity, B, false, out_packed,
-                          out_bits_opt, iters_used_opt, syn_weight_opt, llr_out_opt, nullptr, &q8);
+                          out_bits_opt, iters_used_opt, syn_weight_opt, llr_out_opt, &ar);
 }
 
 int ldpc_decode_layered_q8_device(ldpc_ctx *ctx, int num, float llr_scale, int max_iters,
@@ -2913,10 +2914,10 @@ int ldpc_decode_layered_q8_device(ldpc_ctx *ctx, int num, float llr_scale, int m
                                   uint8_t *d_out_bits_opt, int32_t *d_iters_used_opt,
                                   int32_t *d_syn_weight_opt, float *d_llr_out_opt,
                                   void *hip_stream) {
-  const Q8Params q8{num, llr_scale};
-  return layered_device_impl(ctx, 1.0, max_iters, et_period, LDPC_PREC_F32, d_in, cw_stride,
-                             elem_stride, polarity, B, d_out_packed, d_out_bits_opt,
-                             d_iters_used_opt, d_syn_weight_opt, d_llr_out_opt, hip_stream, &q8);
+  return layered_device_impl(ctx, q8_arith(num, llr_scale), max_iters, et_period, LDPC_PREC_F32,
+                             d_in, cw_stride, elem_stride, polarity, B, d_out_packed,
+                             d_out_bits_opt, d_iters_used_opt, d_syn_weight_opt, d_llr_out_opt,
+                             hip_stream);
 }
 
 int ldpc_ctx_streams(ldpc_ctx *ctx, int n, void **streams_out) {

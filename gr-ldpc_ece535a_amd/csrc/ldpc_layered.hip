@@ -2,228 +2,659 @@
 // (MI355X): one frame per persistent workgroup, the frame's posteriors LQ[N]
 // and check messages R[E] in LDS from the first iteration to the last.
 //
-// The reference has only the flooding schedule and plain min-sum
-// (lib/ldpc_decoder_cb_impl.cc:309-412); this decoder keeps its conventions
-// (Lci = -tx, sign(0) = 0, the DBL_MAX seed of the minimum, decision LQ < 0,
-// min-sum's exit rule :406-408) and changes the schedule: the rows of H are
-// taken layer by layer (ldpc_layers.hpp), each row reading the posteriors the
-// rows before it have already updated, and every check message is multiplied
-// by a normalisation factor.  Per row j with edges e_0..e_{d-1} in ascending
-// column c_0 < ... < c_{d-1}:
+// The reference has only the flooding schedule and plain min-sum in double on
+// one dense 32x64 H (lib/ldpc_decoder_cb_impl.cc:309-412): it has neither a
+// layered schedule, nor structured codes, nor fixed point.  This decoder keeps
+// its conventions (Lci = -tx, decision LQ < 0, min-sum's exit rule :406-408)
+// and changes the schedule: the rows of H are taken layer by layer
+// (ldpc_layers.hpp), each row reading the posteriors the rows before it have
+// already updated, and every check message is normalised.  Per row j with
+// edges e_0..e_{d-1} in ascending column c_0 < ... < c_{d-1}:
 //
 //   q_k  = LQ[c_k] - R[e_k]
-//   s_k  = sign(q_k), P = s_0 * ... * s_{d-1}
-//   lo_k = min(BIG, |q_t| for t != k)          (strict <: NaN and inf never win)
-//   R[e_k]  = a * ((Real)(P * s_k) * lo_k)     (only the multiply by a rounds)
+//   lo_k = min(seed, |q_t| for t != k)
+//   R[e_k]  = the normalised lo_k under the sign of the other places' q
 //   LQ[c_k] = q_k + R[e_k]
 //
 // A thread owns a row of the current layer.  The rows of a layer share no
 // column, so a thread's LQ and R cells are its own until the barrier that ends
 // the layer.  The leave-one-out minimum is the smaller of the row's two
 // smallest |q| (the second where k is the place of the first): the same value,
-// hence the same bits, as the scan over t != k.  No arithmetic here contracts
-// (-ffp-contract=off) and none is transcendental, so the f64 precisions are
-// one kernel.
+// hence the same bits, as the scan over t != k.
+//
+// Nine kernels are one template (layered_kernel) over two choices that share
+// everything else: an arithmetic (FloatArith<double / float>, Q8Arith: the
+// types, the row's scan and message, a sample's load, the decisions) and a
+// route (TableRoute<staged / L2>, CirculantRoute: the tables, which rows a
+// thread runs in a layer and where their columns and messages are, the
+// syndrome).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <limits>
 
 #include "ldpc_layered.hpp"
-#include "ldpc_layered_dev.hpp"
+#include "ldpc_qc.hpp"
 
 namespace ldpc {
 namespace {
 
-struct LyTabs {
-  const uint32_t *rows;
-  const uint16_t *ci;
-  const uint16_t *order;
-  const uint32_t *off;
+// ---- the arithmetics -------------------------------------------------------------
+
+// tx = in * polarity, then Lci = -tx (:149-153, :318-321) as an operation of
+// its own: folded into one multiply by -polarity, a NaN sample would keep the
+// sign that negating tx flips.
+__device__ __forceinline__ float ly_lci(float in, float polarity) {
+  float tx = in * polarity;
+  asm volatile("" : "+v"(tx));
+  return -tx;
+}
+
+// The float contract (include/ldpc_hip.h), Real = double or
+// float, a = scale:
+//
+//   LQ[i] = (Real)Lci_i;  R[e] = 0
+//   s_k  = sign(q_k) (sign(0) = 0), P = s_0 * ... * s_{d-1}
+//   lo_k = min(BIG, |q_t| for t != k)          (strict <: NaN and inf never win;
+//                                               BIG = DBL_MAX / FLT_MAX, the reference's seed)
+//   R[e_k]  = a * ((Real)(P * s_k) * lo_k)     (only the multiply by a rounds)
+//
+// No arithmetic here contracts (-ffp-contract=off) and none is transcendental,
+// so the f64 precisions are one kernel.  The decisions LQ < 0 are taken once
+// per frame into hard[N] behind R, which the epilogue reads.
+template <typename Real>
+struct FloatArith {
+  using Post = Real;  // LQ
+  using Msg = Real;   // R
+  using Reg = Real;   // a q in registers
+  using Par = bool;   // a row's parity of decisions
+  static constexpr bool kHardRegion = true;
+  Real scale;
+
+  // what a place past the row's degree holds: sign +, never below a minimum
+  static __device__ __forceinline__ Reg pad() { return (Real)INFINITY; }
+  static __device__ __forceinline__ int sgn(Real v) { return (v > Real(0)) - (v < Real(0)); }
+
+  // the sign product, the two smallest |q| and the place of the smallest
+  struct Row {
+    int P = 1, at = -1;
+    Real m1 = std::numeric_limits<Real>::max(), m2 = std::numeric_limits<Real>::max();
+  };
+  static __device__ __forceinline__ void scan(Row &s, Real q, int k) {
+    s.P *= sgn(q);
+    const Real v = __builtin_elementwise_abs(q);
+    const bool first = v < s.m1, second = v < s.m2;
+    s.m2 = first ? s.m1 : second ? v : s.m2;
+    s.m1 = first ? v : s.m1;
+    s.at = first ? k : s.at;
+  }
+  __device__ __forceinline__ Real msg(const Row &s, Real q, int k) const {
+    const Real lo = k == s.at ? s.m2 : s.m1;
+    return scale * ((Real)(s.P * sgn(q)) * lo);
+  }
+
+  __device__ __forceinline__ Post sample(float lci) const { return (Real)lci; }
+  static __device__ __forceinline__ void clear(Msg *R, int E, const LayeredLayout &) {
+    for (int e = threadIdx.x; e < E; e += blockDim.x) R[e] = Real(0);
+  }
+  static __device__ __forceinline__ bool decision(Post v) { return v < Real(0); }
+  static __device__ __forceinline__ Par term(Post v) { return v < Real(0); }
+  static __device__ __forceinline__ bool odd(Par x) { return x; }
 };
+
+// The fixed-point contract (include/ldpc_hip.h), num in
+// [1, 16]: the check messages R[E] are int8 and the posteriors LQ[N] int16, so a
+// frame is a16(2 N) + a16(E) + 128 bytes where the float layouts need 5 N + 4 E.
+//
+//   v_i = Lci_i * llr_scale                                      (float)
+//   LQ[i] = v_i is NaN ? 0 : clamp(rint(v_i), -127, 127);  R[e] = 0
+//   s_k  = q_k < 0 ? -1 : +1,  P = s_0 * ... * s_{d-1}
+//   lo_k = min(127, |q_t| for t != k)
+//   R[e_k]  = (P * s_k) * ((lo_k * num + 8) >> 4)
+//
+// All of it is integer arithmetic in 32-bit registers; what is stored fits its
+// type exactly: |R| <= 127, and LQ[c] = Lc_c + the sum of the column's R after
+// every update, so |LQ| <= 127 (dv + 1) <= 32767 (layered_q8_layout checks dv).
+// The sign product is the XOR of the q's sign bits.  The decisions are LQ < 0,
+// read in place: there is no decision array.  Consecutive lanes of the
+// circulant route touch consecutive bytes of R and, up to the wrap, consecutive
+// halfwords of LQ: four and two lanes to a dword.
+struct Q8Arith {
+  using Post = int16_t;
+  using Msg = int8_t;
+  using Reg = int;
+  using Par = int;  // the XOR of a row's posteriors: its sign is the parity
+  static constexpr bool kHardRegion = false;
+  static constexpr int kMax = 127;
+  int num;
+  float llr_scale;
+
+  static __device__ __forceinline__ Reg pad() { return 32767; }
+
+  // The XOR of the q's (its sign bit is that of P), the two smallest |q| below
+  // the seed and the place of the smallest.
+  struct Row {
+    int sg = 0, m1 = kMax, m2 = kMax, at = -1;
+  };
+  static __device__ __forceinline__ void scan(Row &s, int q, int k) {
+    s.sg ^= q;
+    const int v = q < 0 ? -q : q;
+    const bool first = v < s.m1, second = v < s.m2;
+    s.m2 = first ? s.m1 : second ? v : s.m2;
+    s.m1 = first ? v : s.m1;
+    s.at = first ? k : s.at;
+  }
+  __device__ __forceinline__ int msg(const Row &s, int q, int k) const {
+    const int lo = k == s.at ? s.m2 : s.m1;
+    const int mag = (lo * num + 8) >> 4;
+    return (s.sg ^ q) < 0 ? -mag : mag;
+  }
+
+  __device__ __forceinline__ Post sample(float lci) const {
+    const float v = lci * llr_scale;
+    const float c = fminf(fmaxf(rintf(v), -(float)kMax), (float)kMax);
+    return v != v ? (int16_t)0 : (int16_t)(int)c;
+  }
+  // as dwords: R's region is a multiple of 16 bytes
+  static __device__ __forceinline__ void clear(Msg *R, int, const LayeredLayout &lay) {
+    uint32_t *R32 = reinterpret_cast<uint32_t *>(R);
+    const int n = (lay.red - lay.r) >> 2;
+    for (int e = threadIdx.x; e < n; e += blockDim.x) R32[e] = 0u;
+  }
+  static __device__ __forceinline__ bool decision(Post v) { return v < 0; }
+  static __device__ __forceinline__ Par term(Post v) { return v; }
+  static __device__ __forceinline__ bool odd(Par x) { return x < 0; }
+};
+
+// ---- the row update --------------------------------------------------------------
+
+// Rows of at most D places are gathered whole into registers: the row's columns
+// in one batch of independent reads, both operands of every place in a second,
+// where a loop over the places would wait for each read in turn (DESIGN section
+// 7a: such chains are what the on-chip kernels' time is).  Places past d read
+// some column of the code (col_pad) and the message of place 0, and hold
+// Arith::pad(), which leaves the scan's state as it is, so the scan has no
+// branches.  Rr: the row's first message; Addr: where place k's column (col)
+// and message (Rr[msg(k)]) are.
+template <int D, typename Arith, typename Addr>
+__device__ __forceinline__ void row_regs(const Arith &ar, const Addr &ad, int d,
+                                         typename Arith::Post *LQ, typename Arith::Msg *Rr) {
+  using Reg = typename Arith::Reg;
+  int c[D];
+  Reg q[D], rv[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) c[k] = ad.col_pad(k, d);
+  // the messages first: their addresses need no column, so on the table
+  // route they are in flight while the column indices arrive
+#pragma unroll
+  for (int k = 0; k < D; ++k) rv[k] = Rr[ad.msg(k < d ? k : 0)];
+#pragma unroll
+  for (int k = 0; k < D; ++k) q[k] = LQ[c[k]];
+#pragma unroll
+  for (int k = 0; k < D; ++k) q[k] = k < d ? q[k] - rv[k] : Arith::pad();
+  typename Arith::Row s;
+#pragma unroll
+  for (int k = 0; k < D; ++k) Arith::scan(s, q[k], k);
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    if (k < d) {
+      const Reg m = ar.msg(s, q[k], k);
+      Rr[ad.msg(k)] = (typename Arith::Msg)m;
+      LQ[c[k]] = (typename Arith::Post)(q[k] + m);
+    }
+  }
+}
+
+// A longer row: the scan, then q_k again (the same operands, the same bits)
+// and the row's writes.
+template <typename Arith, typename Addr>
+__device__ __forceinline__ void row_loop(const Arith &ar, const Addr &ad, int d,
+                                         typename Arith::Post *LQ, typename Arith::Msg *Rr) {
+  using Reg = typename Arith::Reg;
+  typename Arith::Row s;
+#pragma unroll 4
+  for (int k = 0; k < d; ++k) Arith::scan(s, (Reg)LQ[ad.col(k)] - (Reg)Rr[ad.msg(k)], k);
+#pragma unroll 4
+  for (int k = 0; k < d; ++k) {
+    const int c = ad.col(k);
+    const Reg q = (Reg)LQ[c] - (Reg)Rr[ad.msg(k)];
+    const Reg m = ar.msg(s, q, k);
+    Rr[ad.msg(k)] = (typename Arith::Msg)m;
+    LQ[c] = (typename Arith::Post)(q + m);
+  }
+}
+
+// The per-wave syndrome counts summed over the workgroup: every thread gets
+// the sum.  One barrier; the layers' barriers separate this call's reads of
+// red[] from the next call's writes.
+__device__ __forceinline__ int ly_sum_waves(int cnt, int *red) {
+  const int tid = threadIdx.x, T = blockDim.x;
+  if ((tid & 63) == 0) red[tid >> 6] = cnt;
+  __syncthreads();
+  int w = 0;
+  const int nwaves = T >> 6;
+  for (int i = 0; i < nwaves; ++i) w += red[i];
+  return w;
+}
+
+// ---- the table route -------------------------------------------------------------
+
+constexpr int kRegsShort = 8, kRegsLong = 16;
+static_assert(kRegsLong <= kQcEntPad, "a register row is loaded whole from any entry");
 
 template <typename T>
 __device__ __forceinline__ void ly_copy(T *dst, const T *src, int n) {
   for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
 }
 
-// Rows of at most kRowRegs edges are gathered whole into registers: the
-// row's column indices in one batch of independent LDS reads, its operands in
-// a second, where a loop over the places would wait for each read in turn
-// (such chains are what the on-chip kernels' time is).
-constexpr int kRowRegs = 8;
+// A row of the per-edge tables: ci its first column index, its messages at Rr[k].
+struct TabAddr {
+  const uint16_t *ci;
+  __device__ __forceinline__ int col(int k) const { return ci[k]; }
+  __device__ __forceinline__ int col_pad(int k, int d) const { return ci[k < d ? k : 0]; }
+  __device__ __forceinline__ int msg(int k) const { return k; }
+};
 
-// Syndrome weight of the decisions LQ < 0 (checkFrame :236-253, no
-// threshold), read from the posteriors in LDS: every thread gets the sum
-// (ly_sum_waves: one barrier).
-template <typename Real>
-__device__ __forceinline__ int ly_syndrome(const LyTabs &g, int M, const Real *LQ, int *red) {
-  const int tid = threadIdx.x, T = blockDim.x;
-  int cnt = 0;
-  for (int j0 = 0; j0 < M; j0 += T) {  // uniform trip count: the ballots see whole waves
-    const int j = j0 + tid;
-    bool odd = false;
-    if (j < M) {
-      const uint32_t rec = g.rows[j];
-      const int e0 = rec & 0xffff, d = rec >> 16;
-      if (d > 0 && d <= kRowRegs) {
-        int c[kRowRegs];
-#pragma unroll
-        for (int k = 0; k < kRowRegs; ++k) c[k] = g.ci[e0 + (k < d ? k : 0)];
-#pragma unroll
-        for (int k = 0; k < kRowRegs; ++k) odd ^= (LQ[c[k]] < Real(0)) & (k < d);
-      } else {
-        for (int t = 0; t < d; ++t) odd ^= LQ[g.ci[e0 + t]] < Real(0);
-      }
+// Any plan through per-edge tables (LayeredTables): a thread per row of the
+// layer, rows of at most 8 places in registers and longer ones (up to 32) in
+// two passes.  STAGED: the tables fit behind the frame and are copied to LDS
+// once per launch; otherwise they are read from global memory (L2).
+template <bool STAGED>
+struct TableRoute {
+  using View = LayeredView;
+  const uint32_t *rows;
+  const uint16_t *ci;
+  const uint16_t *order;
+  const uint32_t *off;
+  int M, L;
+
+  __device__ __forceinline__ void init(const View &gv, unsigned char *smem,
+                                       const LayeredLayout &lay) {
+    M = gv.M;
+    L = gv.L;
+    rows = gv.rows;
+    ci = gv.ci;
+    order = gv.order;
+    off = gv.off;
+    if constexpr (STAGED) {
+      uint32_t *s_rows = reinterpret_cast<uint32_t *>(smem + lay.rows);
+      uint16_t *s_ci = reinterpret_cast<uint16_t *>(smem + lay.ci);
+      uint16_t *s_order = reinterpret_cast<uint16_t *>(smem + lay.order);
+      uint32_t *s_off = reinterpret_cast<uint32_t *>(smem + lay.off);
+      ly_copy(s_rows, gv.rows, M);
+      ly_copy(s_ci, gv.ci, gv.E);
+      ly_copy(s_order, gv.order, M);
+      ly_copy(s_off, gv.off, L + 1);
+      rows = s_rows;
+      ci = s_ci;
+      order = s_order;
+      off = s_off;
+      __syncthreads();
     }
-    cnt += __popcll(__ballot(odd));
   }
-  return ly_sum_waves(cnt, red);
+  __device__ __forceinline__ int layers() const { return L; }
+  __device__ __forceinline__ void rewind() {}
+
+  template <typename Arith>
+  __device__ __forceinline__ void run_layer(int l, const Arith &ar, typename Arith::Post *LQ,
+                                            typename Arith::Msg *R) {
+    const int r1 = (int)off[l + 1];
+    for (int r = (int)off[l] + threadIdx.x; r < r1; r += blockDim.x) {
+      const uint32_t rec = rows[order[r]];
+      const int e0 = rec & 0xffff, d = rec >> 16;
+      const TabAddr ad{ci + e0};
+      if (d > 0 && d <= kRegsShort)
+        row_regs<kRegsShort>(ar, ad, d, LQ, R + e0);
+      else
+        row_loop(ar, ad, d, LQ, R + e0);
+    }
+  }
+
+  // Syndrome weight of the decisions (checkFrame :236-253, no threshold), read
+  // from the posteriors in LDS: every thread gets the sum.
+  template <typename Arith>
+  __device__ __forceinline__ int syndrome(const typename Arith::Post *LQ, int *red) const {
+    using Par = typename Arith::Par;
+    const int tid = threadIdx.x, T = blockDim.x;
+    int cnt = 0;
+    for (int j0 = 0; j0 < M; j0 += T) {  // uniform trip count: the ballots see whole waves
+      const int j = j0 + tid;
+      Par x = Par(0);
+      if (j < M) {
+        const uint32_t rec = rows[j];
+        const int e0 = rec & 0xffff, d = rec >> 16;
+        if (d > 0 && d <= kRegsShort) {
+          // every place is read, in one batch; a read under `k < d` is a
+          // branch and a wait per place
+          int c[kRegsShort];
+          Par v[kRegsShort];
+#pragma unroll
+          for (int k = 0; k < kRegsShort; ++k) c[k] = ci[e0 + (k < d ? k : 0)];
+#pragma unroll
+          for (int k = 0; k < kRegsShort; ++k) v[k] = Arith::term(LQ[c[k]]);
+#pragma unroll
+          for (int k = 0; k < kRegsShort; ++k) x ^= k < d ? v[k] : Par(0);
+        } else {
+          for (int t = 0; t < d; ++t) x ^= Arith::term(LQ[ci[e0 + t]]);
+        }
+      }
+      cnt += __popcll(__ballot(Arith::odd(x)));
+    }
+    return ly_sum_waves(cnt, red);
+  }
+};
+
+// ---- the circulant route ---------------------------------------------------------
+
+// The base tables are written before the launch and never during it: read
+// through the constant address space, a uniform index is a scalar load
+// whatever the kernel stores in between (a plain global pointer makes them
+// vector loads here, since the frames' outputs might alias it).
+typedef const uint32_t __attribute__((address_space(4))) *QcWords;
+__device__ __forceinline__ QcWords qc_words(const uint32_t *p) {
+  return (QcWords)(uintptr_t)p;
 }
 
-template <typename Real, bool STAGED>
+// Column of lane i's edge in the circulant w = c * Z | s << 16.
+__device__ __forceinline__ int qc_col(uint32_t w, int i, int Z) {
+  const uint32_t t = (uint32_t)i + (w >> 16);
+  return (int)((w & 0xffffu) + min(t, t - (uint32_t)Z));
+}
+
+// Lane i's row of a block row: place k's column from the entry word w[k] (W:
+// registers or the table itself), its message at Rr[k * Z].  The words past d
+// are other entries of the table or its padding, so their columns are columns
+// of the code.
+template <typename W>
+struct QcAddr {
+  W w;
+  int i, Z;
+  __device__ __forceinline__ int col(int k) const { return qc_col(w[k], i, Z); }
+  __device__ __forceinline__ int col_pad(int k, int) const { return col(k); }
+  __device__ __forceinline__ int msg(int k) const { return k * Z; }
+};
+
+// A quasi-cyclic code (ldpc_qc.hpp) decoded by its block rows.  Layer r is
+// block row r; thread i < Z owns row r * Z + i, threads past Z idle up to the
+// layer's barrier.  The row's k-th edge is at column
+//   c_k * Z + (i + s_k) mod Z  =  c_k * Z + min(t, t - Z),  t = i + s_k
+// (unsigned: t - Z wraps above t where t < Z), with (c_k, s_k) and the degree
+// d_r the same for the whole workgroup: one word per base entry, read through
+// a uniform pointer (scalar loads, the degree and the first eight entries of a
+// block row in one batch), where the table route reads a 16-bit column per
+// edge and can issue the LQ read only once that has returned.  R is kept
+// place-major within the block row, R[(eb_r + k) * Z + i] (eb_r: the base
+// entries before row r), so consecutive lanes touch consecutive cells of R
+// and, up to the wrap, of LQ.  The layout is internal: within a row ascending
+// block column is ascending column, so place k is the contract's k-th edge and
+// every value is the contract's.
+//
+// The degree is uniform over a layer, so every loop over places has a uniform
+// trip count.  Rows of at most 8 places, and of 9 to 16, are gathered whole
+// into registers; longer rows (up to 32) take two passes over their places.
+struct CirculantRoute {
+  using View = LayeredQcView;
+  QcWords rows, ent;
+  int mb, Z;
+  int eb;  // the base entries before the next block row: a running sum, so that
+           // the row's degree and its first entries load side by side
+
+  __device__ __forceinline__ void init(const View &gv, unsigned char *, const LayeredLayout &) {
+    rows = qc_words(gv.rows);
+    ent = qc_words(gv.ent);
+    mb = gv.mb;
+    Z = gv.Z;
+  }
+  __device__ __forceinline__ int layers() const { return mb; }
+  __device__ __forceinline__ void rewind() { eb = 0; }
+
+  template <typename Arith>
+  __device__ __forceinline__ void run_layer(int r, const Arith &ar, typename Arith::Post *LQ,
+                                            typename Arith::Msg *R) {
+    const int tid = threadIdx.x;
+    QcWords e = ent + eb;
+    const int d = (int)(rows[r] & 0xffffu);
+    __builtin_assume(d >= 1);  // the table lists no empty block row
+    // The first eight words whatever d is: one batch of scalar loads and one
+    // wait (a load per place under `k < d` compiles to a wait per place).
+    uint32_t w[kRegsLong];
+#pragma unroll
+    for (int k = 0; k < kRegsShort; ++k) w[k] = e[k];
+    if (tid < Z) {
+      typename Arith::Msg *Rr = R + eb * Z + tid;
+      if (d <= kRegsShort) {
+        row_regs<kRegsShort>(ar, QcAddr<const uint32_t *>{w, tid, Z}, d, LQ, Rr);
+      } else if (d <= kRegsLong) {
+#pragma unroll
+        for (int k = kRegsShort; k < kRegsLong; ++k) w[k] = e[k];
+        row_regs<kRegsLong>(ar, QcAddr<const uint32_t *>{w, tid, Z}, d, LQ, Rr);
+      } else {
+        row_loop(ar, QcAddr<QcWords>{e, tid, Z}, d, LQ, Rr);
+      }
+    }
+    eb += d;
+  }
+
+  // Syndrome weight of the decisions (checkFrame :236-253, no threshold), block
+  // row by block row: thread i combines the decisions at its row's places, a
+  // ballot per block row counts the odd ones, and every thread gets the sum.
+  // Four block rows go side by side: their records, then their first eight
+  // entries, then their LQ reads are each one batch; one block row at a time
+  // is a scalar and an LDS round trip per block row, with nothing else to run
+  // on a one-wave workgroup.  Threads past Z read lane Z - 1's columns and are
+  // left out of the ballot, so the reads sit in no branch.
+  static constexpr int kSynRows = 4;
+
+  template <typename Arith>
+  __device__ __forceinline__ int syndrome(const typename Arith::Post *LQ, int *red) const {
+    using Par = typename Arith::Par;
+    const int tid = threadIdx.x;
+    const int i = min(tid, Z - 1);
+    const bool mine = tid < Z;
+    int cnt = 0;
+    for (int r0 = 0; r0 < mb; r0 += kSynRows) {  // every wave sees every ballot
+      int d[kSynRows];
+      QcWords e[kSynRows];
+      uint32_t w[kSynRows][kRegsShort];
+#pragma unroll
+      for (int s = 0; s < kSynRows; ++s) {
+        const bool ok = r0 + s < mb;
+        const uint32_t rec = rows[ok ? r0 + s : 0];
+        d[s] = ok ? (int)(rec & 0xffffu) : 0;
+        e[s] = ent + (rec >> 16);
+      }
+#pragma unroll
+      for (int s = 0; s < kSynRows; ++s)
+#pragma unroll
+        for (int k = 0; k < kRegsShort; ++k) w[s][k] = e[s][k];
+      Par x[kSynRows];
+#pragma unroll
+      for (int s = 0; s < kSynRows; ++s) {
+        x[s] = Par(0);
+#pragma unroll
+        for (int k = 0; k < kRegsShort; ++k) {
+          const Par v = Arith::term(LQ[qc_col(w[s][k], i, Z)]);
+          x[s] ^= k < d[s] ? v : Par(0);
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < kSynRows; ++s)
+        for (int k = kRegsShort; k < d[s]; ++k) x[s] ^= Arith::term(LQ[qc_col(e[s][k], i, Z)]);
+#pragma unroll
+      for (int s = 0; s < kSynRows; ++s) cnt += __popcll(__ballot(Arith::odd(x[s]) & mine));
+    }
+    return ly_sum_waves(cnt, red);
+  }
+};
+
+// ---- a frame ---------------------------------------------------------------------
+
+// Frame b into LDS: LQ = the samples' Lci in the arithmetic's format, R = 0;
+// ends with the barrier that lets the first layer read them.  The layered
+// entry points take strided frames only (no window lists, no second-polarity
+// half: DecodeArgs::win and pm_half are unset).
+template <typename Arith>
+__device__ __forceinline__ void load_frame(const Arith &ar, const DecodeArgs &a, int64_t b, int N,
+                                           int E, const LayeredLayout &lay,
+                                           typename Arith::Post *LQ, typename Arith::Msg *R) {
+  const int tid = threadIdx.x, T = blockDim.x;
+  const float pol = a.polarity;
+  const float *src = a.in + b * a.cw_stride;
+  for (int i = tid; i < N; i += T) LQ[i] = ar.sample(ly_lci(src[(int64_t)i * a.elem_stride], pol));
+  Arith::clear(R, E, lay);
+  __syncthreads();
+}
+
+// Frame b's outputs (the syndrome's barrier is behind every LQ write): the
+// decisions, the iterations used and the syndrome weight, the float
+// posteriors, and the info bits M.., MSB first (:207-219).
+template <typename Arith>
+__device__ __forceinline__ void store_frame(const DecodeArgs &a, int64_t b, int M, int N, int KB,
+                                            int used, int weight, const typename Arith::Post *LQ,
+                                            uint8_t *hard) {
+  const int tid = threadIdx.x, T = blockDim.x;
+  if constexpr (Arith::kHardRegion) {
+    for (int i = tid; i < N; i += T) hard[i] = Arith::decision(LQ[i]);
+    __syncthreads();
+  }
+  const auto bit = [&](int i) -> uint32_t {
+    if constexpr (Arith::kHardRegion)
+      return hard[i];
+    else
+      return Arith::decision(LQ[i]);
+  };
+  if (tid == 0) {
+    if (a.iters) a.iters[b] = used;
+    if (a.synd) a.synd[b] = weight;
+  }
+  if (a.bits)
+    for (int i = tid; i < N; i += T) a.bits[b * N + i] = bit(i);
+  if (a.llr)
+    for (int i = tid; i < N; i += T) a.llr[b * N + i] = (float)LQ[i];
+  for (int p = tid; p < KB; p += T) {
+    uint32_t o = 0;
+    for (int j = 0; j < 8; ++j) {
+      const int c = M + 8 * p + j;
+      if (c < N) o |= bit(c) << (7 - j);
+    }
+    a.packed[b * KB + p] = (uint8_t)o;
+  }
+}
+
+// The workgroup's next frame (the barrier also ends this frame's LDS reads):
+// a fixed stride, or the stream's counter.
+__device__ __forceinline__ int64_t ly_next_frame(const DecodeArgs &a, int64_t b, int *red) {
+  if (a.static_stride) {
+    __syncthreads();
+    return b + a.waves;
+  }
+  if (threadIdx.x == 0) red[16] = (int)(atomicAdd(a.ticket, 1u) - a.ticket_base);
+  __syncthreads();
+  return (int64_t)a.waves + (int64_t)red[16];
+}
+
+template <typename Arith, typename Route>
 __global__ void __launch_bounds__(kLayeredMaxThreads)
-    layered_decode_kernel(LayeredView gv, DecodeArgs a, LayeredLayout lay, Real scale) {
+    layered_kernel(typename Route::View gv, DecodeArgs a, LayeredLayout lay, Arith ar) {
+  using Post = typename Arith::Post;
+  using Msg = typename Arith::Msg;
   extern __shared__ __align__(16) unsigned char smem[];
-  Real *LQ = reinterpret_cast<Real *>(smem);
-  Real *R = reinterpret_cast<Real *>(smem + lay.r);
+  Post *LQ = reinterpret_cast<Post *>(smem);
+  Msg *R = reinterpret_cast<Msg *>(smem + lay.r);
   uint8_t *hard = smem + lay.hard;
   int *red = reinterpret_cast<int *>(smem + lay.red);
-  const int tid = threadIdx.x, T = blockDim.x;
-  const int M = gv.M, N = gv.N, E = gv.E, NL = gv.L;
-  LyTabs g;
-  if constexpr (STAGED) {
-    uint32_t *rows = reinterpret_cast<uint32_t *>(smem + lay.rows);
-    uint16_t *ci = reinterpret_cast<uint16_t *>(smem + lay.ci);
-    uint16_t *order = reinterpret_cast<uint16_t *>(smem + lay.order);
-    uint32_t *off = reinterpret_cast<uint32_t *>(smem + lay.off);
-    ly_copy(rows, gv.rows, M);
-    ly_copy(ci, gv.ci, E);
-    ly_copy(order, gv.order, M);
-    ly_copy(off, gv.off, NL + 1);
-    g.rows = rows;
-    g.ci = ci;
-    g.order = order;
-    g.off = off;
-    __syncthreads();
-  } else {
-    g.rows = gv.rows;
-    g.ci = gv.ci;
-    g.order = gv.order;
-    g.off = gv.off;
-  }
+  Route route;
+  route.init(gv, smem, lay);
+  const int NL = route.layers();
 
   int64_t b = blockIdx.x;
   while (b < a.B) {
-    ly_load_frame(a, b, N, E, LQ, R);
+    load_frame(ar, a, b, gv.N, gv.E, lay, LQ, R);
     int used = 0, weight = 0;
     for (int h = 0;; ++h) {
+      route.rewind();
       for (int l = 0; l < NL; ++l) {
-        const int r1 = (int)g.off[l + 1];
-        for (int r = (int)g.off[l] + tid; r < r1; r += T) {
-          const uint32_t rec = g.rows[g.order[r]];
-          const int e0 = rec & 0xffff, d = rec >> 16;
-          // the sign product, the two smallest |q| and the place of the smallest
-          int P = 1, at = -1;
-          Real m1 = Lim<Real>::big(), m2 = Lim<Real>::big();
-          if (d > 0 && d <= kRowRegs) {
-            // the whole row in registers; places past d read place 0 again and
-            // hold +inf, which leaves P, m1, m2 and `at` as they are (sign +1,
-            // never below a minimum), so the scan has no branches
-            int c[kRowRegs];
-            Real q[kRowRegs];
-#pragma unroll
-            for (int k = 0; k < kRowRegs; ++k) c[k] = g.ci[e0 + (k < d ? k : 0)];
-#pragma unroll
-            for (int k = 0; k < kRowRegs; ++k) {
-              const Real v = LQ[c[k]] - R[e0 + (k < d ? k : 0)];
-              q[k] = k < d ? v : (Real)INFINITY;
-            }
-#pragma unroll
-            for (int k = 0; k < kRowRegs; ++k) {
-              P *= ly_sgn(q[k]);
-              const Real v = Lim<Real>::abs_(q[k]);
-              const bool first = v < m1, second = v < m2;
-              m2 = first ? m1 : second ? v : m2;
-              m1 = first ? v : m1;
-              at = first ? k : at;
-            }
-#pragma unroll
-            for (int k = 0; k < kRowRegs; ++k) {
-              if (k < d) {
-                const Real lo = k == at ? m2 : m1;
-                const Real m = scale * ((Real)(P * ly_sgn(q[k])) * lo);
-                R[e0 + k] = m;
-                LQ[c[k]] = q[k] + m;
-              }
-            }
-            continue;
-          }
-          for (int k = 0; k < d; ++k) {
-            const Real q = LQ[g.ci[e0 + k]] - R[e0 + k];
-            P *= ly_sgn(q);
-            const Real v = Lim<Real>::abs_(q);
-            if (v < m1) {
-              m2 = m1;
-              m1 = v;
-              at = k;
-            } else if (v < m2) {
-              m2 = v;
-            }
-          }
-          // q_k again (the same operands, the same bits), then the row's writes
-          for (int k = 0; k < d; ++k) {
-            const int c = g.ci[e0 + k];
-            const Real q = LQ[c] - R[e0 + k];
-            const Real lo = k == at ? m2 : m1;
-            const Real m = scale * ((Real)(P * ly_sgn(q)) * lo);
-            R[e0 + k] = m;
-            LQ[c] = q + m;
-          }
-        }
+        route.run_layer(l, ar, LQ, R);
         __syncthreads();
       }
       used = h + 1;
       // the cap first, then the syndrome on multiples of et_period (:406-408)
       const bool last = used == a.max_iters;
       if (last || used % a.et_period == 0) {
-        weight = ly_syndrome(g, M, LQ, red);
+        weight = route.template syndrome<Arith>(LQ, red);
         if (last || weight == 0) break;
       }
     }
-    ly_store_frame(a, b, M, N, gv.KB, used, weight, LQ, hard);
+    store_frame<Arith>(a, b, gv.M, gv.N, gv.KB, used, weight, LQ, hard);
     b = ly_next_frame(a, b, red);
   }
 }
 
-template <typename Real, bool STAGED>
-int launch_kernel(const LayeredView &g, DecodeArgs a, const LayeredLayout &lay, double scale,
+// ---- the launch ------------------------------------------------------------------
+
+// The workgroups the device holds of kernel `fn` at `threads` threads and
+// `bytes` of dynamic LDS (looked up once per kernel and layout: resident ==
+// 0).  The LDS attribute belongs to the kernel, not to the caller: it allows
+// any layout layered_layout accepts.  False on a runtime error.
+bool ly_resident(const void *fn, int threads, int bytes, int &resident) {
+  if (resident != 0) return true;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLayeredLdsLimit) !=
+      hipSuccess)
+    return false;
+  int per_cu = 0, dev = 0, cus = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, (size_t)bytes) !=
+          hipSuccess ||
+      per_cu < 1 || hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      cus < 1)
+    return false;
+  resident = per_cu * cus;
+  return true;
+}
+
+template <typename Arith, typename Route>
+int launch_kernel(const typename Route::View &g, DecodeArgs a, const LayeredLayout &lay, Arith ar,
                   hipStream_t st, int &resident) {
-  const void *fn = (const void *)layered_decode_kernel<Real, STAGED>;
+  const void *fn = (const void *)layered_kernel<Arith, Route>;
   if (!ly_resident(fn, lay.threads, lay.total, resident)) return -3;
   a.waves = (int)std::min<int64_t>(a.B, resident);
-  hipLaunchKernelGGL((layered_decode_kernel<Real, STAGED>), dim3((unsigned)a.waves),
-                     dim3((unsigned)lay.threads), (size_t)lay.total, st, g, a, lay, (Real)scale);
+  hipLaunchKernelGGL((layered_kernel<Arith, Route>), dim3((unsigned)a.waves),
+                     dim3((unsigned)lay.threads), (size_t)lay.total, st, g, a, lay, ar);
   return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+template <typename Route>
+int launch_route(const typename Route::View &g, const DecodeArgs &args, const LayeredLayout &lay,
+                 const LayeredArith &ar, void *stream, int *resident, uint32_t *advance_out) {
+  *advance_out = 0;
+  if (args.B <= 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if (ar.kind == kLayeredQ8)
+    rc = launch_kernel<Q8Arith, Route>(g, args, lay, {ar.num, ar.llr_scale}, st, *resident);
+  else if (ar.kind == kLayeredF32)
+    rc = launch_kernel<FloatArith<float>, Route>(g, args, lay, {(float)ar.scale}, st, *resident);
+  else
+    rc = launch_kernel<FloatArith<double>, Route>(g, args, lay, {ar.scale}, st, *resident);
+  // one add per frame decoded, each workgroup's last being the one past the batch
+  if (rc == 0 && !args.static_stride) *advance_out = (uint32_t)args.B;
+  return rc;
 }
 
 }  // namespace
 
 int launch_layered_decode(const LayeredView &g, const DecodeArgs &args, const LayeredLayout &lay,
-                          double scale, int prec, void *stream, int *resident,
+                          const LayeredArith &ar, void *stream, int *resident,
                           uint32_t *advance_out) {
-  *advance_out = 0;
-  if (args.B <= 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  int rc;
-  if (prec == 1)
-    rc = lay.staged ? launch_kernel<float, true>(g, args, lay, scale, st, resident[1])
-                    : launch_kernel<float, false>(g, args, lay, scale, st, resident[1]);
-  else
-    rc = lay.staged ? launch_kernel<double, true>(g, args, lay, scale, st, resident[0])
-                    : launch_kernel<double, false>(g, args, lay, scale, st, resident[0]);
-  // one add per frame decoded, each workgroup's last being the one past the batch
-  if (rc == 0 && !args.static_stride) *advance_out = (uint32_t)args.B;
-  return rc;
+  return lay.staged ? launch_route<TableRoute<true>>(g, args, lay, ar, stream, resident, advance_out)
+                    : launch_route<TableRoute<false>>(g, args, lay, ar, stream, resident,
+                                                      advance_out);
+}
+
+int launch_layered_decode(const LayeredQcView &g, const DecodeArgs &args, const LayeredLayout &lay,
+                          const LayeredArith &ar, void *stream, int *resident,
+                          uint32_t *advance_out) {
+  return launch_route<CirculantRoute>(g, args, lay, ar, stream, resident, advance_out);
 }
 
 }  // namespace ldpc

@@ -1,7 +1,10 @@
 // ldpc_layered.hpp -- host/device types of the layered normalized min-sum
-// decoder (ldpc_layered.hip): one frame per persistent workgroup, the frame's
+// decoders (ldpc_layered.hip): one frame per persistent workgroup, the frame's
 // posteriors and check messages in LDS, the rows of H taken layer by layer
-// (ldpc_layers.hpp).
+// (ldpc_layers.hpp).  A decode is an arithmetic (LayeredArith: double, float,
+// or int8 messages with int16 posteriors) on a route: per-edge tables for any
+// plan (LayeredView), or the base matrix of a quasi-cyclic code decoded by its
+// block rows (LayeredQcView).
 #pragma once
 
 #include <stdint.h>
@@ -19,30 +22,43 @@ struct LayeredView {
   int M, N, E, KB, L;
 };
 
-// Launches one layered decode of args.B frames on `stream` with the layout
-// `lay` (layered_layout: it fits).  args.ticket / ticket_base / static_stride
-// as in DecodeArgs (`waves` is set here: the resident workgroups).  scale: the
-// normalisation factor, 0 < scale <= 1.  *advance_out: what the launch adds to
-// its counter.  resident[prec == 1]: the workgroups the device holds of each
-// kernel for this layout (0: not looked up yet).  Returns 0, or -3 on a launch
-// error.
-int launch_layered_decode(const LayeredView &g, const DecodeArgs &args, const LayeredLayout &lay,
-                          double scale, int prec, void *stream, int *resident,
-                          uint32_t *advance_out);
-
-// A quasi-cyclic code as the circulant kernel reads it (ldpc_qc.hpp QcTables).
+// A quasi-cyclic code as the circulant route reads it (ldpc_qc.hpp QcTables).
+// E may exceed 16 bits: the base tables hold no edge index.
 struct LayeredQcView {
   const uint32_t *rows;  // mb: degree (>= 1) | entries before << 16, per block row that has any
   const uint32_t *ent;   // per base entry: block column * Z | shift << 16; 16 zero words behind
   int M, N, E, KB, mb, Z;  // mb: the block rows listed in `rows`
 };
 
-// The same launch for a quasi-cyclic code decoded by its block rows
-// (ldpc_layered_qc.hip): `lay` is layered_layout's for mb layers of Z rows,
-// with nothing staged (lay.total == lay.frame: the base tables are read
-// through the scalar cache).  Arguments and result as launch_layered_decode.
-int launch_layered_qc_decode(const LayeredQcView &g, const DecodeArgs &args,
-                             const LayeredLayout &lay, double scale, int prec, void *stream,
-                             int *resident, uint32_t *advance_out);
+enum { kLayeredF64 = 0, kLayeredF32 = 1, kLayeredQ8 = 2 };
+
+// The arithmetic of a decode.  kLayeredF64 / kLayeredF32: `scale` is the
+// normalisation factor, 0 < scale <= 1.  kLayeredQ8: `num` is the
+// normalisation numerator, 1..16 (the factor is num / 16), and `llr_scale` what
+// a sample is multiplied by before it is rounded to an integer in [-127, 127].
+struct LayeredArith {
+  int kind;
+  double scale;
+  int num;
+  float llr_scale;
+};
+
+// Launches one layered decode of args.B frames on `stream` with the layout
+// `lay` (layered_layout, or layered_q8_layout for kLayeredQ8: it fits).
+// args.ticket / ticket_base / static_stride as in DecodeArgs (`waves` is set
+// here: the resident workgroups).  *advance_out: what the launch adds to its
+// counter.  *resident: the workgroups the device holds of the kernel this
+// arithmetic and layout select (0: not looked up yet).  Returns 0, or -3 on a
+// launch error.
+int launch_layered_decode(const LayeredView &g, const DecodeArgs &args, const LayeredLayout &lay,
+                          const LayeredArith &ar, void *stream, int *resident,
+                          uint32_t *advance_out);
+
+// The same for a quasi-cyclic code decoded by its block rows: `lay` is the
+// layout for mb layers of Z rows with nothing staged (lay.total == lay.frame:
+// the base tables are read through the scalar cache).
+int launch_layered_decode(const LayeredQcView &g, const DecodeArgs &args, const LayeredLayout &lay,
+                          const LayeredArith &ar, void *stream, int *resident,
+                          uint32_t *advance_out);
 
 }  // namespace ldpc

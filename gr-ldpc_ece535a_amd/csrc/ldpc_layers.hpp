@@ -56,7 +56,7 @@ struct LayeredLayout {
 bool layered_layout(int M, int N, int E, int dc_max, int L, int max_layer_rows, int prec,
                     LayeredLayout &lay);
 
-// The fixed-point decoder's layout (ldpc_layered_q8.hip): LQ int16[N] at
+// The fixed-point decoder's layout (ldpc_layered.hip Q8Arith): LQ int16[N] at
 // offset 0, R int8[E] at `r`, the reduction words at `red` (`hard` is unused
 // and equals `red`: the decisions are LQ < 0, read in place), every term
 // rounded up to 16 bytes:

@@ -1,6 +1,6 @@
 // ldpc_qc.hpp -- quasi-cyclic codes for the layered decoder: the description
 // (a base matrix of circulant shifts and a lifting size), its expansion to
-// CSR, and the base tables of the circulant kernel (ldpc_layered_qc.hip).
+// CSR, and the base tables of the circulant route (ldpc_layered.hip).
 // Host only, no device needed.
 //
 // A QC code is (mb, nb, Z, shifts): shifts is mb x nb, row-major; -1 is the

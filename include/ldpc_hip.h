@@ -231,7 +231,7 @@ ldpc_ctx *ldpc_create_csr(int M, int N, const int32_t *row_ptr, const int32_t *c
  * path, every entry point working on it unchanged -- and the context remembers
  * the base matrix (ldpc_ctx_qc).  Its layered decodes (ldpc_decode_layered*)
  * take the block rows as their plan and, while that plan is in force, run the
- * circulant kernel (csrc/ldpc_layered_qc.hip); with LDPC_FLAG_QC_TABLES they
+ * circulant kernel (csrc/ldpc_layered.hip); with LDPC_FLAG_QC_TABLES they
  * keep the plan and run the per-edge table kernel.  A code outside the layered
  * kernels' limits still gets a context; its layered decodes alone are refused. */
 ldpc_ctx *ldpc_create_qc(int mb, int nb, int Z, const int32_t *shifts, int flags, int device);

@@ -1,7 +1,7 @@
 """The fixed-point layered min-sum contract ("q8": include/ldpc_hip.h, DESIGN
 section 7d), restated in numpy.
 
-`decode` is what tests hold the kernels (csrc/ldpc_layered_q8.hip,
+`decode` is what tests hold the kernels (csrc/ldpc_layered.hip,
 ldpc_decode_layered_q8*) to, value for value; `decode_scalar` is a second
 transcription in plain Python integers, one place at a time, that pins it
 (tests/test_layered_q8_host.py).  num is an integer in [1, 16].

@@ -1,5 +1,5 @@
 """GPU parity of the fixed-point layered decoder (ldpc_decode_layered_q8*,
-csrc/ldpc_layered_q8.hip): int8 check messages and int16 posteriors in LDS, on
+csrc/ldpc_layered.hip): int8 check messages and int16 posteriors in LDS, on
 the circulant route (a quasi-cyclic context under its block rows) and on the
 per-edge table route (any other context or plan).
 
@@ -156,6 +156,30 @@ def test_table_route_on_a_qc_context(name):
     _eq(b, ref, "table kernel")
     _eq(a, b, "circulant vs table kernel")
     tab.dec.close()
+
+
+def test_table_route_with_tables_in_l2():
+    """The table kernel with its tables left in global memory: Z = 1024, mb = 4,
+    N = 16384, E = 44032 <= 65535 under the block rows.  The frame fits in LDS;
+    the frame and the tables together do not, so nothing is staged."""
+    import ldpc_ece535a as L
+    base = q8.large_base(16)
+    c = _Case("big16t", base, 1024, qc_tables=True)
+    M, N, E, NL = c.csr[0], c.csr[1], c.csr[3].size, base.shape[0]
+    assert (M, N, E, NL) == (4096, 16384, 44032, 4)
+
+    def a16(x):
+        return (x + 15) & ~15
+    frame = a16(2 * N) + a16(E) + 128
+    tables = a16(4 * M) + a16(2 * E) + a16(2 * M) + a16(4 * (NL + 1))
+    assert frame == L.plan_qc_q8(base, 1024)["lds_bytes"] == 76928
+    assert frame <= 160 * 1024 < frame + tables == 189600
+    assert (c.dec.layers == c.plan).all()
+    y = c.frames(136, 8, 3.0)
+    for num in (16, 13):
+        _eq(c.dec.decode_layered_q8(y, num=num, max_iters=5, want_llr=True),
+            q8.decode(c.csr, c.plan, y, 5, num=num), "num %d" % num)
+    c.dec.close()
 
 
 def test_change_of_plan_between_decodes():

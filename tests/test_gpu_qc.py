@@ -1,5 +1,5 @@
 """GPU parity of the layered decoder on quasi-cyclic contexts (ldpc_create_qc,
-ldpc_layered_qc.hip): the block rows as the plan, a thread per row of a block
+ldpc_layered.hip): the block rows as the plan, a thread per row of a block
 row, columns from the base matrix.
 
 Every comparison is against the numpy restatement of the layered contract

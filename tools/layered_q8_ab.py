@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B of the fixed-point layered decoder (ldpc_decode_layered_q8*,
-ldpc_layered_q8.hip) against what the same build already runs on the same
+ldpc_layered.hip) against what the same build already runs on the same
 code.
 
 Codes that fit the float kernels (tools/layered_qc_ab.py's: Z = 27 / N = 648,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of the circulant layered kernel (ldpc_create_qc, ldpc_layered_qc.hip)
+"""A/B of the circulant layered kernel (ldpc_create_qc, ldpc_layered.hip)
 against what the same build already runs on the same code: the per-edge table
 kernel under the same block-row plan (LDPC_FLAG_QC_TABLES), the table kernel
 under the first-fit plan (a CSR context of the expanded H), and flooding
