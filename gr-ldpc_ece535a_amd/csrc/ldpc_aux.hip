@@ -10,7 +10,10 @@
 //                  staircase): s_j = XOR of row j's information bits, parity =
 //                  prefix-XOR of s; one 256-thread block per frame (segmented
 //                  scan through LDS).
-//   random_bits    Philox4x32-10 counter-based bits (seeded, reproducible).
+//   encode_qc      quasi-cyclic codes with a dual-diagonal parity part
+//                  (ldpc_qc_enc.hpp): one workgroup per frame, the frame in
+//                  LDS, the host's step program run level by level.
+//   random_bits   Philox4x32-10 counter-based bits (seeded, reproducible).
 //   bpsk_awgn      x = 2c - 1 + sigma * n, n ~ N(0,1) by Box-Muller on Philox
 //                  output; sigma = sqrt(10^(-EbN0/10)) is the reference's
 //                  convention (apps/ldpc_lapack.cpp:629-636).
@@ -147,6 +150,66 @@ __global__ void __launch_bounds__(256) k_encode_ira(const int32_t *rp, const int
   }
 }
 
+// One workgroup per frame: the frame's nb blocks of Z bytes (a bit each) and
+// the program's scratch blocks in LDS, the step program (ldpc_qc_enc.hpp,
+// qc_enc_pack) interpreted level by level with one barrier each.  A wave takes
+// 64 positions of one step at a time, so the step's words -- destination,
+// sources, shifts -- are the same across the wave and load as scalars; the
+// waves stride over a level's steps x ceil(Z / 64) units.  Frames whose data
+// and codeword rows are 4-byte aligned move as words.
+__global__ void __launch_bounds__(1024) k_encode_qc(const uint32_t *__restrict__ tab, int Z, int M,
+                                                    int K, const uint8_t *__restrict__ data,
+                                                    uint8_t *__restrict__ cw) {
+  extern __shared__ __align__(16) unsigned char buf[];
+  const int t = threadIdx.x, nt = blockDim.x;
+  const int64_t b = blockIdx.x;
+  const int N = M + K;
+  const uint8_t *d = data + b * K;
+  uint8_t *out = cw + b * (int64_t)N;
+  const bool words = ((((uintptr_t)d | (uintptr_t)out) | (unsigned)M | (unsigned)K) & 3u) == 0;
+  if (words) {
+    const uint32_t *d4 = (const uint32_t *)d;
+    uint32_t *b4 = (uint32_t *)(buf + M);
+    for (int i = t; i < K / 4; i += nt) b4[i] = d4[i] & 0x01010101u;
+  } else {
+    for (int i = t; i < K; i += nt) buf[M + i] = d[i] & 1;
+  }
+  __syncthreads();
+  const int lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6), waves = nt >> 6;
+  const int cz = (Z + 63) >> 6;
+  const uint32_t L = tab[0], S0 = tab[1];
+  for (uint32_t l = 0; l < L; ++l) {
+    const uint32_t first = tab[2 + 2 * l], units = tab[3 + 2 * l] * (uint32_t)cz;
+    for (uint32_t u = (uint32_t)wave; u < units; u += (uint32_t)waves) {
+      const uint32_t s = u / (uint32_t)cz;
+      const int i = (int)(u - s * (uint32_t)cz) * 64 + lane;
+      const uint32_t *st = tab + S0 + 3 * (first + s);
+      const uint32_t dst = st[0], sb = st[1], n = st[2];
+      if (i < Z) {
+        uint8_t acc = 0;
+        for (uint32_t k = 0; k < n; ++k) {
+          const uint32_t w = tab[sb + k];
+          int j = i + (int)(w >> 20);
+          j -= j >= Z ? Z : 0;
+          acc ^= buf[(w & 0xFFFFFu) + j];
+        }
+        int j = i + (int)(dst >> 20);
+        j -= j >= Z ? Z : 0;
+        buf[(dst & 0xFFFFFu) + j] = acc;
+      }
+    }
+    __syncthreads();
+  }
+  if (words) {
+    const uint32_t *b4 = (const uint32_t *)buf;
+    uint32_t *o4 = (uint32_t *)out;
+    for (int i = t; i < N / 4; i += nt) o4[i] = b4[i];
+  } else {
+    for (int i = t; i < N; i += nt) out[i] = buf[i];
+  }
+}
+
 inline unsigned blocks_for(int64_t n, int per_block) {
   return (unsigned)((n + per_block - 1) / per_block);
 }
@@ -192,6 +255,20 @@ int launch_encode_ira(const int32_t *rp, const int32_t *ci, int M, int K, const 
                       int B, uint8_t *cw, void *stream) {
   if (B <= 0) return 0;
   k_encode_ira<<<B, 256, 0, (hipStream_t)stream>>>(rp, ci, M, K, data, cw);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_encode_qc(const uint32_t *tab, int Z, int M, int K, int threads, int lds_bytes,
+                     bool *lds_allowed, const uint8_t *data, int B, uint8_t *cw, void *stream) {
+  if (B <= 0) return 0;
+  // more than 64 KiB of dynamic LDS is the kernel's to allow, once
+  if (lds_bytes > 65536 && !*lds_allowed) {
+    if (hipFuncSetAttribute((const void *)k_encode_qc, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            163840) != hipSuccess)
+      return -1;
+    *lds_allowed = true;
+  }
+  k_encode_qc<<<B, threads, (size_t)lds_bytes, (hipStream_t)stream>>>(tab, Z, M, K, data, cw);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

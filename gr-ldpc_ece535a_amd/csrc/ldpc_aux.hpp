@@ -16,6 +16,11 @@ int launch_encode_small(const uint64_t *A, int M, int K, const uint8_t *data, in
 // CSR H whose columns 0..M-1 form the accumulator staircase.
 int launch_encode_ira(const int32_t *rp, const int32_t *ci, int M, int K, const uint8_t *data,
                       int B, uint8_t *cw, void *stream);
+// tab: the step program of a quasi-cyclic code (ldpc_qc_enc.hpp qc_enc_pack);
+// threads and lds_bytes are the program's; *lds_allowed: the kernel has been
+// allowed more than 64 KiB of LDS on this device (set here on first need).
+int launch_encode_qc(const uint32_t *tab, int Z, int M, int K, int threads, int lds_bytes,
+                     bool *lds_allowed, const uint8_t *data, int B, uint8_t *cw, void *stream);
 
 // out[b*N + i] = +-span[(win[b] >> 1) + i]: the N samples of window b, negated
 // when bit 0 of win[b] is set (the block's decode-any-window batches).

@@ -29,6 +29,7 @@
 #include "ldpc_layout.hpp"
 #include "ldpc_layered.hpp"
 #include "ldpc_qc.hpp"
+#include "ldpc_qc_enc.hpp"
 #include "ldpc_onchip.hpp"
 
 using ldpc::ColRec;
@@ -235,9 +236,14 @@ struct ldpc_ctx {
   ldpc::LayeredLayout lay_q8{};
   int q8_resident = 0;      // workgroups the device holds of the kernel lay_q8 selects
   // device encoder (built on first ldpc_encode_device): 1 small (A = H_p^-1 H_d
-  // bit rows in d_encA), 2 IRA staircase, -1 no systematic encoder
+  // bit rows in d_encA), 2 IRA staircase, 3 quasi-cyclic with a dual-diagonal
+  // parity part (the step program of ldpc_qc_enc.hpp in d_enc_qc), -1 no
+  // systematic encoder
   int enc_kind = 0;
   uint64_t *d_encA = nullptr;
+  uint32_t *d_enc_qc = nullptr;
+  int enc_qc_threads = 0, enc_qc_lds = 0;
+  bool enc_qc_lds_allowed = false;
   std::string enc_err;
   std::string err;
 };
@@ -750,11 +756,38 @@ int decode_graph(ldpc_ctx *ctx, const ldpc::DecodeArgs &a, int method, int preci
 // Systematic encoder of the context's H (codeword = [parity (M) | data (K)]):
 // small codes get A = H_p^-1 H_d by Gauss-Jordan over GF(2) (unique when the
 // first M columns are independent, which reorderHMatrix ensures); large codes
-// must have the accumulator staircase in columns 0..M-1 (IRA / DVB-S2).
+// must have the accumulator staircase in columns 0..M-1 (IRA / DVB-S2).  A
+// quasi-cyclic context whose base matrix has an encodable parity part
+// (ldpc_qc_enc.hpp) takes that encoder whatever its size -- the codeword is
+// unique, so the small ones get the same bytes -- and any other falls through
+// to the two rules above.
 int prepare_encoder(ldpc_ctx *ctx) {
   if (ctx->enc_kind > 0) return LDPC_OK;
   if (ctx->enc_kind < 0) return set_err(ctx, LDPC_EUNSUPPORTED, ctx->enc_err);
   const int M = ctx->M, N = ctx->N, K = N - M;
+  ldpc::QcEncProgram prog;
+  if (ctx->qc_Z > 0 &&
+      ldpc::qc_enc_compile(ctx->qc_mb, ctx->qc_nb, ctx->qc_Z, ctx->qc_shifts.data(), prog, nullptr)) {
+    if (prog.lds_bytes() > ldpc::kQcEncLdsLimit) {
+      char buf[200];
+      snprintf(buf, sizeof buf,
+               "quasi-cyclic encoder: the frame and its %d scratch blocks take %lld bytes of LDS "
+               "(limit %lld): no device encoder",
+               prog.scratch, (long long)prog.lds_bytes(), (long long)ldpc::kQcEncLdsLimit);
+      ctx->enc_kind = -1;
+      ctx->enc_err = buf;
+      return set_err(ctx, LDPC_EUNSUPPORTED, ctx->enc_err);
+    }
+    std::vector<uint32_t> tab;
+    ldpc::qc_enc_pack(prog, tab);
+    hipError_t e = hipMalloc(&ctx->d_enc_qc, tab.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_enc_qc, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_err(ctx, e, "encoder upload");
+    ctx->enc_qc_threads = prog.threads();
+    ctx->enc_qc_lds = (int)prog.lds_bytes();
+    ctx->enc_kind = 3;
+    return LDPC_OK;
+  }
   if (!ctx->H.empty() && K <= 256) {
     const int W = (N + 63) / 64;
     std::vector<uint64_t> rows((size_t)M * W, 0);
@@ -1240,6 +1273,7 @@ void ldpc_destroy(ldpc_ctx *ctx) {
   }
   if (ctx->graph_done) (void)hipEventDestroy(ctx->graph_done);
   if (ctx->d_encA) (void)hipFree(ctx->d_encA);
+  if (ctx->d_enc_qc) (void)hipFree(ctx->d_enc_qc);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -1374,6 +1408,10 @@ int ldpc_encode_device(ldpc_ctx *ctx, const uint8_t *d_data_bits, int B, uint8_t
   const int K = ctx->N - ctx->M;
   if (ctx->enc_kind == 1)
     rc = ldpc::launch_encode_small(ctx->d_encA, ctx->M, K, d_data_bits, B, d_codewords, st);
+  else if (ctx->enc_kind == 3)
+    rc = ldpc::launch_encode_qc(ctx->d_enc_qc, ctx->qc_Z, ctx->M, K, ctx->enc_qc_threads,
+                                ctx->enc_qc_lds, &ctx->enc_qc_lds_allowed, d_data_bits, B,
+                                d_codewords, st);
   else
     rc = ldpc::launch_encode_ira(ctx->d_rp ? ctx->d_rp : nullptr, ctx->d_ci, ctx->M, K,
                                  d_data_bits, B, d_codewords, st);
@@ -2805,6 +2843,46 @@ int ldpc_plan_qc(int mb, int nb, int Z, const int32_t *shifts, int precision,
     if (lds_bytes_out_opt) *lds_bytes_out_opt = lay.frame;
     if (threads_out_opt) *threads_out_opt = lay.threads;
     return fits ? 1 : 0;
+  } catch (const std::exception &e) {
+    return set_err(nullptr, LDPC_ENOMEM, e.what());
+  }
+}
+
+int ldpc_plan_qc_encoder(int mb, int nb, int Z, const int32_t *shifts, int *core_out_opt,
+                         int *levels_out_opt, int64_t *lds_bytes_out_opt) {
+  g_create_error.clear();
+  std::string why;
+  if (!ldpc::qc_check(mb, nb, Z, shifts, &why))
+    return set_err(nullptr, LDPC_EINVAL, "bad quasi-cyclic code: " + why);
+  try {
+    ldpc::QcEncProgram prog;
+    if (!ldpc::qc_enc_compile(mb, nb, Z, shifts, prog, &why)) {
+      set_err(nullptr, LDPC_EUNSUPPORTED, "no quasi-cyclic encoder: " + why);
+      return 0;
+    }
+    if (core_out_opt) *core_out_opt = prog.core;
+    if (levels_out_opt) *levels_out_opt = prog.levels();
+    if (lds_bytes_out_opt) *lds_bytes_out_opt = prog.lds_bytes();
+    return 1;
+  } catch (const std::exception &e) {
+    return set_err(nullptr, LDPC_ENOMEM, e.what());
+  }
+}
+
+int ldpc_encode_qc(int mb, int nb, int Z, const int32_t *shifts, const uint8_t *data_bits, int B,
+                   uint8_t *codewords_out) {
+  g_create_error.clear();
+  std::string why;
+  if (!ldpc::qc_check(mb, nb, Z, shifts, &why))
+    return set_err(nullptr, LDPC_EINVAL, "bad quasi-cyclic code: " + why);
+  if (B < 0 || (B > 0 && (!data_bits || !codewords_out)))
+    return set_err(nullptr, LDPC_EINVAL, "bad encoder arguments");
+  try {
+    ldpc::QcEncProgram prog;
+    if (!ldpc::qc_enc_compile(mb, nb, Z, shifts, prog, &why))
+      return set_err(nullptr, LDPC_EUNSUPPORTED, "no quasi-cyclic encoder: " + why);
+    ldpc::qc_enc_run(prog, data_bits, B, codewords_out);
+    return LDPC_OK;
   } catch (const std::exception &e) {
     return set_err(nullptr, LDPC_ENOMEM, e.what());
   }

@@ -13,10 +13,11 @@ lib/libldpc_hip.so; there is no CPU fallback.
 from ._capi import (  # noqa: F401
     FLAG_NO_REORDER, FLAG_QC_TABLES, METHOD_BITFLIP, METHOD_HARD, METHOD_LOGDOMAIN, METHOD_SUMPRODUCT,
     PREC_F32, PREC_F64, PREC_F64_FAST, PREC_F64_LIBM, Decoder, LdpcError, bpsk_awgn, check_frame, count_bit_errors,
-    default_h, encode, plan_layers, plan_layers_q8, plan_layout, plan_qc, plan_qc_q8, random_bits, reorder_h,
+    default_h, encode, encode_qc, plan_layers, plan_layers_q8, plan_layout, plan_qc, plan_qc_encoder, plan_qc_q8,
+    random_bits, reorder_h,
 )
 from .blocks import (  # noqa: F401,E402
     STATE_IN_SYNC, STATE_IN_SYNC_INVERTED, STATE_OUT_OF_SYNC, ldpc_decoder_cb, ldpc_encoder_bc,
 )
 from . import flowgraph  # noqa: F401,E402
-from .codes import qc_dual_diagonal, qc_encode, qc_expand  # noqa: F401,E402
+from .codes import qc_dual_diagonal, qc_encode, qc_expand, qc_parity_core  # noqa: F401,E402

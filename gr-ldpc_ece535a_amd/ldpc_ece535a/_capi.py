@@ -88,6 +88,8 @@ SIGNATURES = {
     "ldpc_ring_info": (_i, [_vp, _i32p, _i32p]),
     "ldpc_plan_layers": (_i, [_i, _i, _i32p, _i32p, _i, _i32p, _i32p, _i64p, _i32p]),
     "ldpc_plan_qc": (_i, [_i, _i, _i, _i32p, _i, _i32p, _i32p, _i64p, _i32p]),
+    "ldpc_plan_qc_encoder": (_i, [_i, _i, _i, _i32p, _i32p, _i32p, _i64p]),
+    "ldpc_encode_qc": (_i, [_i, _i, _i, _i32p, _u8p, _i, _u8p]),
     "ldpc_create_qc": (_vp, [_i, _i, _i, _i32p, _i, _i]),
     "ldpc_ctx_qc": (_i, [_vp, _i32p, _i32p, _i32p, _i32p]),
     "ldpc_ctx_layers": (_i, [_vp, _i32p]),
@@ -297,6 +299,40 @@ def plan_qc_q8(base, Z):
     fits = _check(lib().ldpc_plan_qc_q8(base.shape[0], base.shape[1], Z, _p(base, _i32p),
                                         ctypes.byref(lds), ctypes.byref(threads)))
     return dict(fits=bool(fits), lds_bytes=lds.value, threads=threads.value)
+
+
+def plan_qc_encoder(base, Z):
+    """ldpc_plan_qc_encoder (host only, no GPU): whether the quasi-cyclic code
+    (base, Z) has a systematic encoder here (a dual-diagonal core, a block
+    lower triangular extension, or both: include/ldpc_hip.h).  dict with
+    encodable, core (the core's block rows, 0 for none), levels (of the step
+    program: the device encoder's barriers), lds_bytes (of its workgroup) and,
+    when not encodable, reason (naming the block row and column that broke the
+    form).  Raises for a bad description."""
+    base, Z = _qc_base(base, Z)
+    core, levels, lds = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+    ok = _check(lib().ldpc_plan_qc_encoder(base.shape[0], base.shape[1], Z, _p(base, _i32p),
+                                           ctypes.byref(core), ctypes.byref(levels),
+                                           ctypes.byref(lds)))
+    out = dict(encodable=bool(ok), core=core.value, levels=levels.value, lds_bytes=lds.value)
+    if not ok:
+        out["reason"] = (lib().ldpc_last_error(None) or b"").decode()
+    return out
+
+
+def encode_qc(base, Z, data_bits):
+    """ldpc_encode_qc (host only, no GPU): (B, K) data bits (bit 0 of each byte
+    counts) -> (B, N) codewords [parity | data] of the quasi-cyclic code
+    (base, Z), by the step program the device encoder runs."""
+    base, Z = _qc_base(base, Z)
+    mb, nb = base.shape
+    d = np.ascontiguousarray(np.atleast_2d(data_bits), np.uint8)
+    if d.shape[1] != (nb - mb) * Z:
+        raise LdpcError("LDPC_EINVAL: data_bits must be (B, (nb - mb) * Z)")
+    out = np.zeros((d.shape[0], nb * Z), np.uint8)
+    _check(lib().ldpc_encode_qc(mb, nb, Z, _p(base, _i32p), _p(d, _u8p), d.shape[0],
+                                _p(out, _u8p)))
+    return out
 
 
 class Decoder:

@@ -20,7 +20,16 @@ private copies.
 
     python -m ldpc_ece535a.ber [--frames 30] [--iterations 5]
                                [--ebn0 -7:10:0.5] [--code default|dvbs2] [--json out]
+                               [--qc MC,ME,NB,Z,DEG,SEED | --qc dual:MB,NB,Z,DEG,SEED]
                                [--layered SCALE] [--layered-q8 NUM[:LLR_SCALE]]
+
+--qc sweeps a quasi-cyclic code in place of --code: codes.qc_parity_core (a
+dual-diagonal core of MC block rows and ME extension rows, the 802.11n /
+802.16e / 5G-NR parity shape) or, with "dual:", codes.qc_dual_diagonal, NB block
+columns lifted by Z, information columns of degree DEG, drawn from SEED.  The
+decoder is Decoder(qc=...), so the frames are encoded by the quasi-cyclic
+device encoder and the layered curves run the circulant kernel.  The base
+matrices are synthetic, and the JSON's "code" field says so.
 
 --layered SCALE adds a fifth curve, "LayeredMinSum": the layered normalized
 min-sum decoder (ldpc_decode_layered_device) at that scale, same iteration
@@ -100,6 +109,26 @@ def sweep(dec=None, ebn0=DEFAULT_EBN0, frames=30, iterations=5, seed=0, precisio
     return out
 
 
+def qc_code(spec):
+    """(base, Z, label) of a --qc argument: "MC,ME,NB,Z,DEG,SEED"
+    (codes.qc_parity_core) or "dual:MB,NB,Z,DEG,SEED" (codes.qc_dual_diagonal)."""
+    from . import codes
+    kind, _, nums = spec.rpartition(":")
+    try:
+        v = [int(x) for x in nums.split(",")]
+    except ValueError:
+        v = []
+    if kind == "dual" and len(v) == 5:
+        base, Z = codes.qc_dual_diagonal(*v), v[2]
+        label = "QC dual-diagonal mb=%d nb=%d Z=%d deg=%d seed=%d" % tuple(v)
+    elif kind == "" and len(v) == 6:
+        base, Z = codes.qc_parity_core(*v), v[3]
+        label = "QC parity-core mc=%d me=%d nb=%d Z=%d deg=%d seed=%d" % tuple(v)
+    else:
+        raise ValueError("--qc takes MC,ME,NB,Z,DEG,SEED or dual:MB,NB,Z,DEG,SEED")
+    return base, Z, label + " (synthetic base matrix)"
+
+
 def octave(ebn0, res):
     """The reference program's Octave output (apps/ldpc_lapack.cpp:707-811)."""
     f = lambda v: "%.4g" % v  # noqa: E731  (std::cout.precision(4))
@@ -142,6 +171,10 @@ def main(argv=None):
     ap.add_argument("--iterations", type=int, default=5)
     ap.add_argument("--ebn0", default="-7:10:0.5")
     ap.add_argument("--code", choices=["default", "dvbs2"], default="default")
+    ap.add_argument("--qc", default=None, metavar="MC,ME,NB,Z,DEG,SEED",
+                    help="a synthetic quasi-cyclic code in place of --code: a parity core of MC "
+                         "block rows and ME extension rows (or dual:MB,NB,Z,DEG,SEED, the "
+                         "lower-triangular dual diagonal)")
     ap.add_argument("--precision", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--json", default=None)
@@ -158,7 +191,14 @@ def main(argv=None):
     # torch first: it then shares its HIP runtime with libldpc_hip.so (see
     # INTEGRATION.md, "One HIP runtime per process")
     import torch  # noqa: F401
-    if a.code == "dvbs2":
+    code = a.code
+    if a.qc is not None:
+        try:
+            base, Z, code = qc_code(a.qc)
+        except ValueError as e:
+            ap.error(str(e))
+        dec = _capi.Decoder(qc=(base, Z))
+    elif a.code == "dvbs2":
         from . import codes
         dec = _capi.Decoder(csr=codes.dvbs2_like(0))
     else:
@@ -169,7 +209,7 @@ def main(argv=None):
     sys.stdout.write(octave(grid, res))
     if a.json:
         json.dump({"ebn0": grid, "frames": a.frames, "iterations": a.iterations,
-                   "code": a.code, "results": res}, open(a.json, "w"), indent=1)
+                   "code": code, "results": res}, open(a.json, "w"), indent=1)
     return 0
 
 

@@ -122,6 +122,8 @@ def syndrome_weight(csr, bits):
 # No standard base graph is available offline; qc_dual_diagonal() draws one with
 # the dual-diagonal parity part of the 802.11n / 802.16e families from a seed.
 # Results on it are labelled "QC dual-diagonal (synthetic base matrix)".
+# qc_parity_core() draws the families' real parity shape (a weight-3 block
+# column beside the dual diagonal, extension rows below), likewise synthetic.
 
 def qc_expand(base, Z):
     """CSR (M, N, row_ptr, col_idx) of the code of base matrix `base` lifted by
@@ -153,6 +155,39 @@ def qc_dual_diagonal(mb, nb, Z, info_deg, seed):
         S[r, r] = 0
         if r >= 1:
             S[r, r - 1] = 0
+    for c in range(mb, nb):
+        rows = rng.choice(mb, size=min(info_deg, mb), replace=False)
+        S[rows, c] = rng.integers(0, Z, size=rows.size)
+    return S
+
+
+def qc_parity_core(mc, me, nb, Z, info_deg, seed, a=1, b=0, x=None):
+    """Seeded (mc + me, nb) base matrix with the parity part of the 802.11n /
+    802.16e / 5G-NR families, which ldpc_encode_device and _capi.encode_qc
+    encode: a core of mc block rows (0 for none, else >= 3) -- block column k,
+    1 <= k < mc, holds shift 0 at (k-1, k) and (k, k); block column 0 holds
+    shift a at (0, 0) and (mc-1, 0) and shift b at (x, 0), 0 < x < mc-1 (default
+    mc // 2) -- and me extension rows, each with its diagonal entry at a drawn
+    shift and up to two drawn entries left of it.  The information block
+    columns (mc + me..nb-1) are drawn as qc_dual_diagonal draws them.  Results
+    on it are labelled "QC parity-core (synthetic base matrix)"."""
+    mb = mc + me
+    if mc < 0 or mc in (1, 2) or me < 0 or mb < 1 or nb <= mb:
+        raise ValueError("need mc = 0 or mc >= 3, me >= 0, mc + me >= 1 and nb > mc + me")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    S = np.full((mb, nb), -1, np.int32)
+    if mc:
+        x = mc // 2 if x is None else int(x)
+        if not (0 < x < mc - 1 and 0 <= a < Z and 0 <= b < Z):
+            raise ValueError("need 0 < x < mc - 1 and a, b in [0, Z)")
+        for k in range(1, mc):
+            S[k - 1, k] = S[k, k] = 0
+        S[0, 0] = S[mc - 1, 0] = a
+        S[x, 0] = b
+    for r in range(mc, mb):
+        S[r, r] = rng.integers(0, Z)
+        left = rng.choice(r, size=min(2, r), replace=False) if r else np.zeros(0, np.int64)
+        S[r, left] = rng.integers(0, Z, size=left.size)
     for c in range(mb, nb):
         rows = rng.choice(mb, size=min(info_deg, mb), replace=False)
         S[rows, c] = rng.integers(0, Z, size=rows.size)

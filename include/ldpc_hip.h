@@ -27,7 +27,9 @@
  *   ldpc_alist_read         a runtime H source in place of the compiled-in matrices
  *                           (lib/ldpc_decoder_cb_impl.cc:60-102, apps/test_data.h)
  *   ldpc_encode_device      makeParityCheck on the GPU (lib/ldpc_encoder_bc_impl.cc:275-294;
- *                           IRA accumulator codes for SURVEY config 4)
+ *                           IRA accumulator codes for SURVEY config 4; dual-diagonal
+ *                           quasi-cyclic codes, with ldpc_plan_qc_encoder and
+ *                           ldpc_encode_qc as its host side)
  *   ldpc_random_bits, ldpc_bpsk_awgn, ldpc_count_bit_errors
  *                           the BER program's source bits, BPSK + AWGN and
  *                           biterr (apps/ldpc_lapack.cpp:603-650, :508-517) on the GPU
@@ -208,6 +210,37 @@ int ldpc_plan_layers(int M, int N, const int32_t *row_ptr, const int32_t *col_id
 int ldpc_plan_qc(int mb, int nb, int Z, const int32_t *shifts, int precision,
                  int32_t *row_ptr_out_opt, int32_t *col_idx_out_opt, int64_t *lds_bytes_out_opt,
                  int *threads_out_opt);
+
+/* Says, without a GPU, whether a quasi-cyclic code (described as for
+ * ldpc_plan_qc) has a systematic encoder here.  The codeword is [parity (M) |
+ * data (K)]: parity block columns 0..mb-1, information block columns mb..nb-1;
+ * with rot(v, s)[i] = v[(i + s) mod Z] and P = shifts[:, :mb], the parity part
+ * must have one of two forms, for a core size mc (0, or 3 <= mc <= mb):
+ *   extension (block rows mc..mb-1): P[r][r] >= 0 at any shift, nothing right
+ *     of it, and block rows 0..mc-1 hold nothing in block columns mc..mb-1
+ *     (mc = 0: block lower triangular);
+ *   core (the 802.11n / 802.16e / 5G-NR shape): block column k, 1 <= k < mc,
+ *     holds exactly P[k-1][k] = P[k][k] = 0 inside the core, and block column
+ *     0 exactly P[0][0] = P[mc-1][0] = a and P[x][0] = b, one 0 < x < mc-1;
+ *     the core's columns are free in the extension rows.
+ * Either parity part is invertible, so the codeword of given data is unique.
+ * Returns 1 when encodable -- core_out receives mc, levels_out the dependency
+ * levels of the encoder's step program (each one barrier of the device
+ * encoder) and lds_bytes_out the LDS its workgroup declares, (nb + mc) * Z
+ * rounded up to 16: ldpc_encode_device takes the code when that is within
+ * 163840 -- and 0 when not, ldpc_last_error(NULL) naming the block row and
+ * block column that broke the form; LDPC_EINVAL for a bad description, as
+ * ldpc_plan_qc.  (Replaces nothing in the reference, whose encoder solves one
+ * dense 32x64 H, lib/ldpc_encoder_bc_impl.cc:275-294.) */
+int ldpc_plan_qc_encoder(int mb, int nb, int Z, const int32_t *shifts, int *core_out_opt,
+                         int *levels_out_opt, int64_t *lds_bytes_out_opt);
+
+/* Encodes B frames of such a code on the host (no GPU; the same step program
+ * the device encoder runs): data_bits B x K bytes, bit 0 of each counting ->
+ * codewords_out B x N bytes 0/1 = [parity | data].  LDPC_EUNSUPPORTED
+ * (ldpc_last_error(NULL)) for a code ldpc_plan_qc_encoder answers with 0. */
+int ldpc_encode_qc(int mb, int nb, int Z, const int32_t *shifts, const uint8_t *data_bits, int B,
+                   uint8_t *codewords_out);
 
 /* ---- device context ----------------------------------------------- */
 
@@ -614,8 +647,13 @@ int ldpc_set_work_limit(ldpc_ctx *ctx, int64_t bytes);
  * order (for a reordered H the encoder block's [parity; data] output,
  * lib/ldpc_encoder_bc_impl.cc:153-165).  Small codes: any H whose first M
  * columns are independent; large codes: IRA / DVB-S2-style H (columns
- * 0..M-1 the accumulator staircase), else LDPC_EUNSUPPORTED.  Enqueued on
- * hip_stream (NULL = the context's stream). */
+ * 0..M-1 the accumulator staircase), else LDPC_EUNSUPPORTED.  A quasi-cyclic
+ * context (ldpc_create_qc) of any size whose base matrix ldpc_plan_qc_encoder
+ * accepts is encoded from the base matrix, one workgroup per frame with the
+ * frame in LDS (LDPC_EUNSUPPORTED, the bytes in the message, when the frame
+ * and its scratch blocks exceed 163840 bytes); one it does not accept falls
+ * under the two rules above.  Enqueued on hip_stream (NULL = the context's
+ * stream). */
 int ldpc_encode_device(ldpc_ctx *ctx, const uint8_t *d_data_bits, int B,
                        uint8_t *d_codewords, void *hip_stream);
 
