@@ -1,7 +1,7 @@
 // ldpc_kernels.hpp -- shared host/device types of the MI355X decode path.
 //
 // The decoder's view of H is held as per-edge / per-column records in HBM,
-// built once per context (ldpc_capi.hip) from the reordered dense H of
+// built once per context (ldpc_capi_create.hip) from the reordered dense H of
 // lib/ldpc_decoder_cb_impl.cc:98-106.  Edges are numbered in CSR order
 // (row-major, ascending column), which is the order the reference's dense
 // scans visit them.

@@ -63,7 +63,7 @@ def threads():
 
 def kernel_shape(M, N, E, dc, dv):
     """(slots, NW, DCN, DVN, cols) of the small-code kernel: kernel_shape of
-    csrc/ldpc_capi.hip and launch_slots of csrc/ldpc_kernels.hip."""
+    csrc/ldpc_capi_create.hip and launch_slots of csrc/ldpc_kernels.hip."""
     S = (E + 63) // 64
     NW = 1 if N <= 64 else 4
     low = NW == 1 and dc <= 6 and dv <= 3 and S <= 4

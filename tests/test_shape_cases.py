@@ -49,7 +49,7 @@ def test_restated_dispatch_matches_the_sources():
     mw = k[k.index("static int launch_mw_slots"):k.index("static int launch_slots")]
     assert sorted(int(s) for s in re.findall(r"launch_mw<PREC, METHOD, (\d), NW>", mw)) == gen
     assert re.findall(r"launch_nw<(\d)>\(code", k) == ["1", "4"]
-    capi = source("ldpc_capi.hip")
+    capi = source("ldpc_capi_create.hip")
     assert "nw == 1 && dc_max <= 6 && dv_max <= 3 && slots <= 4" in capi
     assert "ctx->nw = N <= 64 ? 1 : 4;" in capi
     for name in ("ldpc_ring.hip", "ldpc_serve.hip"):
