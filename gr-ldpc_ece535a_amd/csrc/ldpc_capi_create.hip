@@ -66,16 +66,6 @@ void ldpc_ctx::Onchip::release() {
 
 namespace {
 
-// The loop lengths the small-code kernel is built with for this code
-// (ldpc_kernels.hip launch_slots), and whether sum-product runs its
-// column-centric form (cols_kernel).
-void kernel_shape(int nw, int slots, int dc_max, int dv_max, int &dcn, int &dvn, bool &cols) {
-  const bool low = nw == 1 && dc_max <= 6 && dv_max <= 3 && slots <= 4;
-  dcn = low ? 5 : ldpc::kDcMax - 1;
-  dvn = low ? 3 : ldpc::kDvMax;
-  cols = nw == 1 && dvn <= slots;
-}
-
 // Edge / column / row tables of the decoder's H (see ldpc_kernels.hpp), at
 // the cells and positions plan_layout chooses (search false: the plain CSR
 // layout, LDPC_FLAG_PLAIN_LAYOUT).
@@ -122,11 +112,12 @@ int build_tables(ldpc_ctx *ctx, std::vector<EdgeRowRec> &erecs, std::vector<Edge
   code.K = N - M;
   code.KB = (code.K + 7) / 8;
 
-  int dcn, dvn;
-  bool cols_k;
-  kernel_shape(nw, slots, code.dc_max, code.dv_max, dcn, dvn, cols_k);
-  const ldpc::EdgeLayout lay = ldpc::plan_layout(M, N, erow, ecol, slots, nw, dcn, dvn, cols_k,
-                                                 search);
+  // the loop lengths the small-code kernels are instantiated with for this
+  // code, and whether sum-product runs its column-centric form: the one
+  // shape rule (ldpc_kernels.hpp) the launchers dispatch by
+  const ldpc::KernelShape shape = ldpc::kernel_shape(nw, slots, code.dc_max, code.dv_max);
+  const ldpc::EdgeLayout lay = ldpc::plan_layout(M, N, erow, ecol, slots, nw, shape.dcn, shape.dvn,
+                                                 shape.cols, search);
   const std::vector<int> &cell = lay.slot, &pos = lay.pos;
   if (cell_out) *cell_out = cell;
   int *model = ctx->small.layout_model;

@@ -1,6 +1,6 @@
 // ldpc_frame.hpp -- the small-code frame decoder (one 64-lane wave, one
-// frame), shared by the batch kernels (ldpc_kernels.hip) and the block
-// walker's decoders (ldpc_walk.hip).  Device code only.
+// frame), shared by the batch kernels (ldpc_kernels.hip), the frame ring
+// (ldpc_ring.hip) and the window server (ldpc_serve.hip).  Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -114,15 +114,11 @@ __device__ __forceinline__ uint32_t lds_at(const uint32_t (&p)[W], int k) {
 
 __host__ __device__ constexpr size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
 
-// Sum-product runs column-centric when that computes no more tanh calls than
-// the edge form (64 NW DVN <= 64 S; the reference's H: 192 = 192).
+// Whether this instantiation runs sum-product column-centric (cols_form,
+// ldpc_kernels.hpp: the rule the host's layout planner uses too).
 template <int METHOD, int S, int NW, int DVN>
 __host__ __device__ constexpr bool cols_kernel() {
-#ifdef LDPC_NO_COLS
-  return false;
-#else
-  return METHOD == 1 && NW == 1 && DVN <= S;
-#endif
+  return cols_form(METHOD, S, NW, DVN);
 }
 
 // Per-wave LDS slice (the workgroup's waves never share LDS), regions as
@@ -165,14 +161,15 @@ struct WaveTables {
 // Frames with a non-finite sample keep the selects (FIN = false).
 // What decode_frame hands back: the syndrome weight (wave-uniform) and, in
 // lanes < KB, packed output byte `lane`.  OUT = false: nothing is stored
-// (the block walker's decoders publish these themselves, ldpc_walk.hip).
+// (the ring and the window server publish these themselves).
 struct FrameResult {
   int weight;
   uint32_t byte;
   int used;  // iterations executed
 };
-// FAIR = false: a build that never manages issue priority (the throughput
-// build: fair_cycles is 0 there), so the clock reads and the state they need
+// FAIR = false: a build that never manages issue priority (the batch
+// kernels' throughput build, batch_minb in ldpc_kernels.hip: fair_cycles is 0
+// there; the ring and the server), so the clock reads and the state they need
 // are compiled out.
 template <int PREC, int METHOD, int S, int NW, int DCN = kDcMax - 1, int DVN = kDvMax,
           bool FIN = false, typename Real = typename Math<PREC>::Real, bool OUT = true,
@@ -829,6 +826,38 @@ __device__ __forceinline__ FrameResult decode_frame(const CodeView &code, const 
   return FrameResult{weight, o, used};
 }
 
+// decode_frame on the samples the caller loaded: a sum-product frame whose
+// samples are all finite (one ballot per frame) takes the FIN = true build.
+// The ring and the server call it; decode_small_kernel keeps a copy of this
+// body and of wave_setup below (see there).
+template <int PREC, int METHOD, int S, int NW, int DCN, int DVN, bool OUT, bool FAIR,
+          typename Real = typename Math<PREC>::Real>
+__device__ __forceinline__ FrameResult decode_samples(const CodeView &code, const DecodeArgs &a,
+                                                      const int64_t b, WaveTables<S, NW> &wt,
+                                                      Real *tb, Real *eb, Real *rb, Real *sb,
+                                                      const int lane,
+                                                      const typename Math<PREC>::Tab *logtab,
+                                                      const float (&xin)[NW],
+                                                      const int (&colq)[NW],
+                                                      const uint32_t (&ppos)[2]) {
+  FrameResult fr;
+  if constexpr (METHOD == 1) {
+    bool bad = false;
+#pragma unroll
+    for (int q = 0; q < NW; ++q) bad |= !__builtin_isfinite(xin[q]);
+    if (__ballot(bad) == 0)
+      fr = decode_frame<PREC, METHOD, S, NW, DCN, DVN, true, Real, OUT, FAIR>(
+          code, a, b, wt, tb, eb, rb, sb, lane, logtab, xin, colq, ppos);
+    else
+      fr = decode_frame<PREC, METHOD, S, NW, DCN, DVN, false, Real, OUT, FAIR>(
+          code, a, b, wt, tb, eb, rb, sb, lane, logtab, xin, colq, ppos);
+  } else {
+    fr = decode_frame<PREC, METHOD, S, NW, DCN, DVN, false, Real, OUT, FAIR>(
+        code, a, b, wt, tb, eb, rb, sb, lane, logtab, xin, colq, ppos);
+  }
+  return fr;
+}
+
 // Frame b's first sample and polarity (DecodeArgs::pm_half: the second half
 // of a both-polarities launch re-reads the first half's windows negated).
 __device__ __forceinline__ const float *frame_src(const DecodeArgs &a, int64_t b, float &pol) {
@@ -925,7 +954,7 @@ __device__ __forceinline__ void wave_setup(const CodeView &code, unsigned char *
   }
 }
 
-// LDS of the workgroup-per-frame kernels (decode_mw_kernel, serve_mw_kernel):
+// LDS of the workgroup-per-frame kernels (decode_mw_kernel, serve_kernel):
 // tb / eb per edge cell, per-wave rb / sb, the frame slot
 template <typename Real, int S, int NW>
 struct MwLayout {

@@ -24,6 +24,7 @@
 // Arithmetic follows the reference operation for operation (same operand
 // order, no contraction: built with -ffp-contract=off), in double
 // (LDPC_PREC_F64) or float (LDPC_PREC_F32).
+#include "ldpc_dispatch.hpp"
 #include "ldpc_frame.hpp"
 
 namespace ldpc {
@@ -44,10 +45,7 @@ __device__ uint64_t g_timeline[4 * kTimelineFrames];
 // default, 1, gives the same register budget)
 #define LDPC_SMALL_MIN_BLOCKS (kWavesPerBlock >= 4 ? 1 : 12 / kWavesPerBlock)
 #endif
-#ifndef LDPC_TP_MINB
-#define LDPC_TP_MINB 4  // throughput build: waves per SIMD the register budget allows
-#endif
-// MINB = 4 (four waves per SIMD, <= 128 VGPRs): the throughput build of the
+// MINB = LDPC_TP_MINB (four waves per SIMD, <= 128 VGPRs): the throughput build of the
 // sum-product f64 kernel (several launches in flight share the CUs); one
 // launch at a time runs faster with the larger register budget
 // (profiles/round2/layout/ab_min_blocks.txt).
@@ -71,7 +69,10 @@ __global__ void __launch_bounds__(kThreads, MINB)
   if (w >= a.waves || b >= a.B) return;
   int64_t bend = b + c;  // end of the wave's current claim
 
-  // the wave's view of the code, in registers
+  // the wave's view of the code, in registers: wave_setup (ldpc_frame.hpp),
+  // spelled out.  The call moves the VGPR / AGPR counts of three
+  // instantiations of this kernel (profiles/round17/small_dispatch_isa.txt),
+  // so the copy stays until that is settled; keep the two in step.
   WaveTables<S, NW> wt;
 #pragma unroll
   for (int s = 0; s < S; ++s) {
@@ -168,11 +169,16 @@ __global__ void __launch_bounds__(kThreads, MINB)
 #pragma unroll
     for (int q = 0; q < NW; ++q)
       xin[q] = colq[q] >= 0 ? src[(int64_t)colq[q] * a.elem_stride] * pol : 0.0f;
+    // decode_samples (ldpc_frame.hpp), spelled out: through the call this
+    // kernel's frame prologue compiled to other instructions (same registers),
+    // and the min-sum launch latencies at B = 16 and 256 measured 0.7-0.9 %
+    // slower, outside the parent's spread (profiles/round17/small_dispatch_ab.txt,
+    // job 1; with this copy they are back, job 2).  Keep the two in step.
     if constexpr (METHOD == 1) {
       bool bad = false;
 #pragma unroll
       for (int q = 0; q < NW; ++q) bad |= !__builtin_isfinite(xin[q]);
-      // the throughput build runs with fair_cycles 0 (launch_slots)
+      // the throughput build runs with fair_cycles 0 (batch_minb)
       constexpr bool kFair = MINB != LDPC_TP_MINB;
       if (__ballot(bad) == 0)
         decode_frame<PREC, METHOD, S, NW, DCN, DVN, true, Real, true, kFair>(
@@ -265,6 +271,8 @@ __global__ void __launch_bounds__(64 * S) decode_mw_kernel(CodeView code, Decode
           if (a.llr) a.llr[b * N + c] = (float)post[q];
         }
       }
+      // (mw_packed_byte, spelled out: the call changes this kernel's register
+      // counts in 75 instantiations, profiles/round17/small_dispatch_isa.txt)
       for (int p = lane; p < code.KB; p += 64) {
         uint32_t o = 0;
 #pragma unroll
@@ -321,79 +329,80 @@ static int launch_mw(const CodeView &code, const DecodeArgs &a, hipStream_t st) 
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-template <int PREC, int METHOD, int NW>
-static int launch_mw_slots(const CodeView &code, const DecodeArgs &a, int slots, hipStream_t st) {
-  switch (slots) {
-    case 1: return launch_mw<PREC, METHOD, 1, NW>(code, a, st);
-    case 2: return launch_mw<PREC, METHOD, 2, NW>(code, a, st);
-    case 3: return launch_mw<PREC, METHOD, 3, NW>(code, a, st);
-    case 4: return launch_mw<PREC, METHOD, 4, NW>(code, a, st);
-    case 5: return launch_mw<PREC, METHOD, 5, NW>(code, a, st);
-    case 6: return launch_mw<PREC, METHOD, 6, NW>(code, a, st);
-    case 7: return launch_mw<PREC, METHOD, 7, NW>(code, a, st);
-    case 8: return launch_mw<PREC, METHOD, 8, NW>(code, a, st);
-    default: return -2;
-  }
+namespace {
+
+// The batch launcher's policy over dispatch_small (ldpc_dispatch.hpp): every
+// slot count; methods 2 and 3 (below, launch_decode) have one kernel per NW.
+constexpr int kBatchSlotsMax = kSlotsMax;
+// MINB of cell C.  Throughput mode (no issue-priority management: fair_cycles
+// is 0) runs the 4-waves-per-SIMD build of the low-degree sum-product f64
+// kernels at 3 and 4 slots.
+template <class C>
+constexpr int batch_minb(bool fair) {
+  return C::LOW && (C::PREC == 0 || C::PREC == 3) && C::METHOD == 1 && (C::S == 3 || C::S == 4) &&
+                 !fair
+             ? LDPC_TP_MINB
+             : LDPC_SMALL_MIN_BLOCKS;
 }
 
-template <int PREC, int METHOD, int NW>
-static int launch_slots(const CodeView &code, const DecodeArgs &a, int slots, hipStream_t st) {
-  // low-degree codes (dc <= 6, dv <= 3: the reference's H) with one column
-  // slot get loops sized to their degrees
-  if constexpr (NW == 1 && METHOD <= 1) {
-    if (code.dc_max <= 6 && code.dv_max <= 3) {
-      // throughput mode (no issue-priority management): the 4-waves-per-SIMD build
-      if constexpr ((PREC == 0 || PREC == 3) && METHOD == 1)
-        if (a.fair_cycles == 0) switch (slots) {
-            case 3: return launch_one<PREC, METHOD, 3, NW, 5, 3, LDPC_TP_MINB>(code, a, st);
-            case 4: return launch_one<PREC, METHOD, 4, NW, 5, 3, LDPC_TP_MINB>(code, a, st);
-            default: break;
-          }
-      switch (slots) {
-        case 1: return launch_one<PREC, METHOD, 1, NW, 5, 3>(code, a, st);
-        case 2: return launch_one<PREC, METHOD, 2, NW, 5, 3>(code, a, st);
-        case 3: return launch_one<PREC, METHOD, 3, NW, 5, 3>(code, a, st);
-        case 4: return launch_one<PREC, METHOD, 4, NW, 5, 3>(code, a, st);
-        default: break;
-      }
-    }
+struct LaunchOne {
+  const CodeView &code;
+  const DecodeArgs &a;
+  hipStream_t st;
+  template <class C>
+  int operator()(C) const {
+    constexpr int kTp = batch_minb<C>(false), kFairMinb = batch_minb<C>(true);
+    if constexpr (kTp != kFairMinb)
+      if (a.fair_cycles == 0)
+        return launch_one<C::PREC, C::METHOD, C::S, C::NW, C::DCN, C::DVN, kTp>(code, a, st);
+    return launch_one<C::PREC, C::METHOD, C::S, C::NW, C::DCN, C::DVN, kFairMinb>(code, a, st);
   }
-  switch (slots) {
-    case 1: return launch_one<PREC, METHOD, 1, NW>(code, a, st);
-    case 2: return launch_one<PREC, METHOD, 2, NW>(code, a, st);
-    case 3: return launch_one<PREC, METHOD, 3, NW>(code, a, st);
-    case 4: return launch_one<PREC, METHOD, 4, NW>(code, a, st);
-    case 5: return launch_one<PREC, METHOD, 5, NW>(code, a, st);
-    case 6: return launch_one<PREC, METHOD, 6, NW>(code, a, st);
-    case 7: return launch_one<PREC, METHOD, 7, NW>(code, a, st);
-    case 8: return launch_one<PREC, METHOD, 8, NW>(code, a, st);
-    default: return -2;
-  }
-}
+};
 
+// bit-flip (2) and hard decision (3): batch-only, one kernel per NW
 template <int NW>
-static int launch_nw(const CodeView &code, const DecodeArgs &a, int method, int prec, int slots,
-                     bool mw, hipStream_t st) {
-  if (mw && method == 1) {
-    if (prec == 1) return launch_mw_slots<1, 1, NW>(code, a, slots, st);
-    if (prec == 2) return launch_mw_slots<2, 1, NW>(code, a, slots, st);
-    if (prec == 3) return launch_mw_slots<3, 1, NW>(code, a, slots, st);
-    return launch_mw_slots<0, 1, NW>(code, a, slots, st);
+int launch_hard(const CodeView &code, const DecodeArgs &a, int method, hipStream_t st) {
+  return method == 2 ? launch_one<1, 2, 1, NW>(code, a, st) : launch_one<1, 3, 1, NW>(code, a, st);
+}
+
+// the workgroup-per-frame kernel has the generic loops only
+struct LaunchMw {
+  const CodeView &code;
+  const DecodeArgs &a;
+  hipStream_t st;
+  template <class C>
+  int operator()(C) const {
+    return launch_mw<C::PREC, C::METHOD, C::S, C::NW>(code, a, st);
   }
-  if (mw && method == 0)
-    return prec == 1 ? launch_mw_slots<1, 0, NW>(code, a, slots, st)
-                     : launch_mw_slots<0, 0, NW>(code, a, slots, st);
-  if (method == 3) return launch_one<1, 3, 1, NW>(code, a, st);
-  if (method == 2) return launch_one<1, 2, 1, NW>(code, a, st);
-  if (method == 1) {
-    if (prec == 1) return launch_slots<1, 1, NW>(code, a, slots, st);
-    if (prec == 2) return launch_slots<2, 1, NW>(code, a, slots, st);
-    if (prec == 3) return launch_slots<3, 1, NW>(code, a, slots, st);
-    return launch_slots<0, 1, NW>(code, a, slots, st);
+};
+
+}  // namespace
+
+int cu_count(int dev) {
+  static std::atomic<int> cus[64];
+  if (dev < 0 || dev >= 64) return 256;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (!n) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
+      n = 256;
+    cus[dev].store(n, std::memory_order_relaxed);
   }
-  // min-sum has no transcendentals: both f64 modes are the same kernel
-  return prec == 1 ? launch_slots<1, 0, NW>(code, a, slots, st)
-                   : launch_slots<0, 0, NW>(code, a, slots, st);
+  return n;
+}
+
+int resident_per_cu(std::atomic<int> &once, const void *fn, int threads, size_t lds, int cap) {
+  int per_cu = once.load(std::memory_order_relaxed);
+  if (!per_cu) {
+    if (lds > 65536 &&
+        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return 0;
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, threads, lds) != hipSuccess || n < 1)
+      n = 1;
+    per_cu = std::min(n, cap);
+    once.store(per_cu, std::memory_order_relaxed);
+  }
+  return per_cu;
 }
 
 int launch_decode(const CodeView &code, const DecodeArgs &args, int method, int prec, int slots,
@@ -402,15 +411,9 @@ int launch_decode(const CodeView &code, const DecodeArgs &args, int method, int 
   *advance_out = 0;
   if (args.B <= 0) return 0;
   DecodeArgs a = args;
-  // CUs of the current device, looked up once per device
-  static int cus_of[64] = {0};
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-    if (!cus_of[dev] &&
-        hipDeviceGetAttribute(&cus_of[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus_of[dev] = 256;
-    cus = cus_of[dev];
-  }
+  // CUs of the current device
+  int dev = 0;
+  const int cus = hipGetDevice(&dev) == hipSuccess ? cu_count(dev) : 256;
 #ifndef LDPC_SMALL_WPC
 #define LDPC_SMALL_WPC 12
 #endif
@@ -444,9 +447,16 @@ int launch_decode(const CodeView &code, const DecodeArgs &args, int method, int 
   // starts at once: claims of several frames would serialise a small batch)
   const int64_t waves_max = (int64_t)waves_per_cu * cus;
   a.claim = mw || a.static_stride || a.B < 4 * waves_max ? 1 : ring_claim(method, prec);
-  if (nw != 1 && nw != 4) return -2;
-  const int rc = nw == 1 ? launch_nw<1>(code, a, method, prec, slots, mw, st)
-                         : launch_nw<4>(code, a, method, prec, slots, mw, st);
+  int rc = -2;
+  if (mw && method <= 1)
+    rc = dispatch_small<kBatchSlotsMax>(method, prec, slots, nw, kernel_shape(nw, slots, kDcMax, kDvMax),
+                                        LaunchMw{code, a, st});
+  else if (method == 2 || method == 3)
+    rc = nw == 1 ? launch_hard<1>(code, a, method, st) : nw == 4 ? launch_hard<4>(code, a, method, st) : -2;
+  else
+    rc = dispatch_small<kBatchSlotsMax>(method, prec, slots, nw,
+                                        kernel_shape(nw, slots, code.dc_max, code.dv_max),
+                                        LaunchOne{code, a, st});
   if (rc == 0 && !a.static_stride)
     *advance_out = (uint32_t)(a.claim * ((a.B + a.claim - 1) / a.claim));
   return rc;

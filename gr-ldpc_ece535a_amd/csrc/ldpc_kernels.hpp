@@ -25,6 +25,34 @@ constexpr int kNMax = 256;         // 4 x 64-bit hard-decision words
 constexpr int kMMax = 256;         // 4 row slots per lane
 constexpr uint16_t kNone = 0xFFFF;
 
+// Sum-product runs column-centric when that computes no more tanh calls than
+// the edge form (64 NW DVN <= 64 S; the reference's H: 192 = 192).
+constexpr bool cols_form(int method, int slots, int nw, int dvn) {
+#ifdef LDPC_NO_COLS
+  return false;
+#else
+  return method == 1 && nw == 1 && dvn <= slots;
+#endif
+}
+
+// The shape rule of the small-code kernels, stated once.  Low-degree codes
+// (dc <= 6, dv <= 3: the reference's H) with one column word get loops sized
+// to their degrees: dcn row neighbours and dvn column entries instead of the
+// records' 7 and 4.  plan_layout places every edge cell for these loop
+// lengths (kernel_shape of ldpc_capi_create.hip) and dispatch_small
+// (ldpc_dispatch.hpp) instantiates the kernels with them, so the two cannot
+// disagree.  cols: whether sum-product runs its column-centric form.
+struct KernelShape {
+  bool low;
+  int dcn, dvn;
+  bool cols;
+};
+constexpr KernelShape kernel_shape(int nw, int slots, int dc_max, int dv_max) {
+  const bool low = nw == 1 && dc_max <= 6 && dv_max <= 3 && slots <= 4;
+  const int dcn = low ? 5 : kDcMax - 1, dvn = low ? 3 : kDvMax;
+  return KernelShape{low, dcn, dvn, cols_form(1, slots, nw, dvn)};
+}
+
 // One edge (j, i) of H, split in two 16/8-byte records so each pass reads
 // its half with one LDS load.  rn: the other edges of row j in ascending
 // column order -- the order of the product T *= tanh(M(j,k)/2) at :507-511

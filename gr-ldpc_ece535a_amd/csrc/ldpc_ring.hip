@@ -36,6 +36,7 @@
 // is one system-scope 8-byte store.
 #include <atomic>
 
+#include "ldpc_dispatch.hpp"
 #include "ldpc_frame.hpp"
 
 namespace ldpc {
@@ -283,21 +284,8 @@ __global__ void __launch_bounds__(kThreads, MINB) ring_kernel(CodeView code, Rin
 #ifdef LDPC_TIMELINE
     const uint64_t t_f1 = ticks();  // (samples loaded and the claim issued)
 #endif
-    FrameResult fr;
-    if constexpr (METHOD == 1) {
-      bool bad = false;
-#pragma unroll
-      for (int q = 0; q < NW; ++q) bad |= !__builtin_isfinite(xin[q]);
-      if (__ballot(bad) == 0)
-        fr = decode_frame<PREC, METHOD, S, NW, DCN, DVN, true, Real, false, false>(
-            code, a, f, wt, tb, eb, rb, sb, lane, logtab, xin, colq, ppos);
-      else
-        fr = decode_frame<PREC, METHOD, S, NW, DCN, DVN, false, Real, false, false>(
-            code, a, f, wt, tb, eb, rb, sb, lane, logtab, xin, colq, ppos);
-    } else {
-      fr = decode_frame<PREC, METHOD, S, NW, DCN, DVN, false, Real, false, false>(
-          code, a, f, wt, tb, eb, rb, sb, lane, logtab, xin, colq, ppos);
-    }
+    const FrameResult fr = decode_samples<PREC, METHOD, S, NW, DCN, DVN, false, false>(
+        code, a, f, wt, tb, eb, rb, sb, lane, logtab, xin, colq, ppos);
     // the next claim, taken when the current one's last frame is done: a
     // claim taken at a frame's start waited for the frame (up to 50
     // iterations), and at a session's end the last tickets sat with waves
@@ -369,89 +357,33 @@ __global__ void __launch_bounds__(kThreads, MINB) ring_kernel(CodeView code, Rin
     if (pend_n) flush();
 }
 
-int cus_of(int dev) {
-  static std::atomic<int> cus[64];
-  if (dev < 0 || dev >= 64) return 256;
-  int n = cus[dev].load(std::memory_order_relaxed);
-  if (!n) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
-      n = 256;
-    cus[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
-}
-
 template <int PREC, int METHOD, int S, int NW, int DCN, int DVN, int MINB>
 int launch_r(const CodeView &code, const RingArgs &r, int dev, hipStream_t st, int *wg) {
   typedef typename Math<PREC>::Real Real;
   const size_t lds = Layout<Real, METHOD, S, NW, DVN>::total;
-  const void *fn = (const void *)ring_kernel<PREC, METHOD, S, NW, DCN, DVN, MINB>;
-  static std::atomic<int> per_cu_once{0};  // resident workgroups per CU (computed once)
-  int per_cu = per_cu_once.load(std::memory_order_relaxed);
-  if (!per_cu) {
-    if (lds > 65536 &&
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return -3;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, kThreads, lds) != hipSuccess || n < 1)
-      n = 1;
-    // the register budget's waves per SIMD bound the workgroups too (a
-    // workgroup past the resident ones only starts when one leaves: a speed
-    // matter, never a hang -- no wave waits on another)
-    per_cu = std::min(n, std::max(1, 4 * MINB / kWavesPerBlock));
-    per_cu_once.store(per_cu, std::memory_order_relaxed);
-  }
-  const int blocks = per_cu * cus_of(dev);
+  static std::atomic<int> once{0};
+  // the register budget's waves per SIMD bound the workgroups too (a
+  // workgroup past the resident ones only starts when one leaves: a speed
+  // matter, never a hang -- no wave waits on another)
+  const int per_cu =
+      resident_per_cu(once, (const void *)ring_kernel<PREC, METHOD, S, NW, DCN, DVN, MINB>, kThreads,
+                      lds, std::max(1, 4 * MINB / kWavesPerBlock));
+  if (!per_cu) return -3;
+  const int blocks = per_cu * cu_count(dev);
   *wg = blocks;
   hipLaunchKernelGGL((ring_kernel<PREC, METHOD, S, NW, DCN, DVN, MINB>), dim3((unsigned)blocks),
                      dim3(kThreads), lds, st, code, r);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-#ifndef LDPC_TP_MINB
-#define LDPC_TP_MINB 4  // four waves per SIMD (<= 128 VGPRs): the throughput build
-#endif
-
-template <int PREC, int METHOD, int NW>
-int ring_slots(const CodeView &code, const RingArgs &r, int slots, int dev, hipStream_t st, int *wg) {
-  // low-degree codes (the reference's H) get loops sized to their degrees,
-  // and four waves per SIMD (ldpc_kernels.hip launch_slots' throughput build)
-  if constexpr (NW == 1) {
-    if (code.dc_max <= 6 && code.dv_max <= 3) switch (slots) {
-        case 1: return launch_r<PREC, METHOD, 1, NW, 5, 3, LDPC_TP_MINB>(code, r, dev, st, wg);
-        case 2: return launch_r<PREC, METHOD, 2, NW, 5, 3, LDPC_TP_MINB>(code, r, dev, st, wg);
-        case 3: return launch_r<PREC, METHOD, 3, NW, 5, 3, LDPC_TP_MINB>(code, r, dev, st, wg);
-        case 4: return launch_r<PREC, METHOD, 4, NW, 5, 3, LDPC_TP_MINB>(code, r, dev, st, wg);
-        default: break;
-      }
-  }
-  constexpr int D = kDcMax - 1, V = kDvMax;
-  switch (slots) {
-    case 1: return launch_r<PREC, METHOD, 1, NW, D, V, 2>(code, r, dev, st, wg);
-    case 2: return launch_r<PREC, METHOD, 2, NW, D, V, 2>(code, r, dev, st, wg);
-    case 3: return launch_r<PREC, METHOD, 3, NW, D, V, 2>(code, r, dev, st, wg);
-    case 4: return launch_r<PREC, METHOD, 4, NW, D, V, 2>(code, r, dev, st, wg);
-    case 5: return launch_r<PREC, METHOD, 5, NW, D, V, 2>(code, r, dev, st, wg);
-    case 6: return launch_r<PREC, METHOD, 6, NW, D, V, 2>(code, r, dev, st, wg);
-    case 7: return launch_r<PREC, METHOD, 7, NW, D, V, 2>(code, r, dev, st, wg);
-    case 8: return launch_r<PREC, METHOD, 8, NW, D, V, 2>(code, r, dev, st, wg);
-    default: return -2;
-  }
-}
-
-template <int NW>
-int ring_nw(const CodeView &code, const RingArgs &r, int method, int prec, int slots, int dev,
-            hipStream_t st, int *wg) {
-  if (method == 1) {
-    if (prec == 1) return ring_slots<1, 1, NW>(code, r, slots, dev, st, wg);
-    if (prec == 2) return ring_slots<2, 1, NW>(code, r, slots, dev, st, wg);
-    if (prec == 3) return ring_slots<3, 1, NW>(code, r, slots, dev, st, wg);
-    return ring_slots<0, 1, NW>(code, r, slots, dev, st, wg);
-  }
-  if (method == 0)  // min-sum: both f64 modes are the same arithmetic
-    return prec == 1 ? ring_slots<1, 0, NW>(code, r, slots, dev, st, wg)
-                     : ring_slots<0, 0, NW>(code, r, slots, dev, st, wg);
-  return -2;
+// The ring's policy over dispatch_small (ldpc_dispatch.hpp): min-sum and
+// sum-product, every slot count.
+constexpr int kRingSlotsMax = kSlotsMax;
+// MINB of cell C: low-degree codes (the reference's H) run four waves per
+// SIMD, as the batch kernels' throughput build (batch_minb, ldpc_kernels.hip)
+template <class C>
+constexpr int ring_minb() {
+  return C::LOW ? LDPC_TP_MINB : 2;
 }
 
 }  // namespace
@@ -459,9 +391,12 @@ int ring_nw(const CodeView &code, const RingArgs &r, int method, int prec, int s
 int launch_ring(const CodeView &code, const RingArgs &r, int method, int prec, int slots, int nw,
                 int device, void *stream, int *workgroups_out) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (nw == 1) return ring_nw<1>(code, r, method, prec, slots, device, st, workgroups_out);
-  if (nw == 4) return ring_nw<4>(code, r, method, prec, slots, device, st, workgroups_out);
-  return -2;
+  return dispatch_small<kRingSlotsMax>(
+      method, prec, slots, nw, kernel_shape(nw, slots, code.dc_max, code.dv_max), [&](auto cell) {
+        typedef decltype(cell) C;
+        return launch_r<C::PREC, C::METHOD, C::S, C::NW, C::DCN, C::DVN, ring_minb<C>()>(
+            code, r, device, st, workgroups_out);
+      });
 }
 
 }  // namespace ldpc

@@ -36,6 +36,7 @@
 // (MI355X_MICROARCH.md, inter-workgroup visibility, R2).
 #include <atomic>
 
+#include "ldpc_dispatch.hpp"
 #include "ldpc_frame.hpp"
 
 namespace ldpc {
@@ -383,21 +384,8 @@ __global__ void __launch_bounds__(64 * S, kServeWavesPerSimd) serve_kernel(CodeV
         float xin[NW];
 #pragma unroll
         for (int q = 0; q < NW; ++q) xin[q] = colq[q] >= 0 ? src[colq[q]] * sgn : 0.0f;
-        FrameResult fr;
-        if constexpr (METHOD == 1) {
-          bool bad = false;
-#pragma unroll
-          for (int q = 0; q < NW; ++q) bad |= !__builtin_isfinite(xin[q]);
-          if (__ballot(bad) == 0)
-            fr = decode_frame<PREC, METHOD, S, NW, DCN, DVN, true, Real, false, false>(
-                code, a, 0, wt, tb, eb, rb, sb, lane, logtab, xin, colq, ppos);
-          else
-            fr = decode_frame<PREC, METHOD, S, NW, DCN, DVN, false, Real, false, false>(
-                code, a, 0, wt, tb, eb, rb, sb, lane, logtab, xin, colq, ppos);
-        } else {
-          fr = decode_frame<PREC, METHOD, S, NW, DCN, DVN, false, Real, false, false>(
-              code, a, 0, wt, tb, eb, rb, sb, lane, logtab, xin, colq, ppos);
-        }
+        const FrameResult fr = decode_samples<PREC, METHOD, S, NW, DCN, DVN, false, false>(
+            code, a, 0, wt, tb, eb, rb, sb, lane, logtab, xin, colq, ppos);
         uint32_t pk = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -411,91 +399,37 @@ __global__ void __launch_bounds__(64 * S, kServeWavesPerSimd) serve_kernel(CodeV
   }
 }
 
-// CUs of the context's device (not the calling thread's current one: the
-// block relaunches a server from its own thread)
-int cus_of_device(int dev) {
-  static std::atomic<int> cus_of[64];
-  if (dev < 0 || dev >= 64) return 256;
-  int n = cus_of[dev].load(std::memory_order_relaxed);
-  if (!n) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
-      n = 256;
-    cus_of[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
-}
-
+// `device`: the context's (not the calling thread's current one: the block
+// relaunches a server from its own thread)
 template <int PREC, int METHOD, int S, int NW, int DCN, int DVN>
 int launch_s(const CodeView &code, const DecodeArgs &a, const ServeArgs &s, int device,
              hipStream_t st, int *wg) {
   typedef typename Math<PREC>::Real Real;
   // the two forms' LDS, overlaid
   const size_t lds = serve_lds_main<Real, METHOD, S, NW, DVN>();
-  const void *fn = (const void *)serve_kernel<PREC, METHOD, S, NW, DCN, DVN>;
-  // resident decoder workgroups per CU (the same on every MI355X of a box;
-  // computed once, racing threads compute the same value)
-  static std::atomic<int> per_cu_once{0};
-  int per_cu = per_cu_once.load(std::memory_order_relaxed);
-  if (!per_cu) {
-    if (lds > 65536 &&
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return -3;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 64 * S, lds) != hipSuccess || n < 1)
-      n = 1;
-    // the API can count more than the hardware admits (SGPR-limited waves,
-    // MI355X_MICROARCH.md "Residency"): workgroups past the resident ones
-    // only start once the launch ends, and rounds go to the decoders that
-    // started (the census), so this is a speed matter only
-    per_cu = std::min(n, 4 * kServeWavesPerSimd / S);
-    per_cu_once.store(per_cu, std::memory_order_relaxed);
-  }
+  static std::atomic<int> once{0};
+  // resident decoder workgroups per CU.  The API can count more than the
+  // hardware admits (SGPR-limited waves, MI355X_MICROARCH.md "Residency"):
+  // workgroups past the resident ones only start once the launch ends, and
+  // rounds go to the decoders that started (the census), so this is a speed
+  // matter only
+  const int per_cu =
+      resident_per_cu(once, (const void *)serve_kernel<PREC, METHOD, S, NW, DCN, DVN>, 64 * S, lds,
+                      4 * kServeWavesPerSimd / S);
+  if (!per_cu) return -3;
   const int blocks = (s.blocks_per_cu > 0 ? std::min(per_cu, s.blocks_per_cu) : per_cu) *
-                     cus_of_device(device);
+                     cu_count(device);
   *wg = blocks - 1;
   hipLaunchKernelGGL((serve_kernel<PREC, METHOD, S, NW, DCN, DVN>), dim3((unsigned)blocks),
                      dim3(64 * S), lds, st, code, a, s);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-template <int PREC, int METHOD, int NW>
-int serve_slots(const CodeView &code, const DecodeArgs &a, const ServeArgs &s, int slots,
-                int dev, hipStream_t st, int *wg) {
-  // low-degree codes (the reference's H) get loops sized to their degrees, as
-  // the batch kernels (ldpc_kernels.hip launch_slots)
-  if constexpr (NW == 1) {
-    if (code.dc_max <= 6 && code.dv_max <= 3) switch (slots) {
-        case 1: return launch_s<PREC, METHOD, 1, NW, 5, 3>(code, a, s, dev, st, wg);
-        case 2: return launch_s<PREC, METHOD, 2, NW, 5, 3>(code, a, s, dev, st, wg);
-        case 3: return launch_s<PREC, METHOD, 3, NW, 5, 3>(code, a, s, dev, st, wg);
-        case 4: return launch_s<PREC, METHOD, 4, NW, 5, 3>(code, a, s, dev, st, wg);
-        default: break;
-      }
-  }
-  constexpr int D = kDcMax - 1, V = kDvMax;
-  switch (slots) {
-    case 1: return launch_s<PREC, METHOD, 1, NW, D, V>(code, a, s, dev, st, wg);
-    case 2: return launch_s<PREC, METHOD, 2, NW, D, V>(code, a, s, dev, st, wg);
-    case 3: return launch_s<PREC, METHOD, 3, NW, D, V>(code, a, s, dev, st, wg);
-    case 4: return launch_s<PREC, METHOD, 4, NW, D, V>(code, a, s, dev, st, wg);
-    default: return -2;  // workgroups of more than 4 waves: launches
-  }
-}
-
-template <int NW>
-int serve_nw(const CodeView &code, const DecodeArgs &a, const ServeArgs &s, int method, int prec,
-             int slots, int dev, hipStream_t st, int *wg) {
-  if (method == 1) {
-    if (prec == 1) return serve_slots<1, 1, NW>(code, a, s, slots, dev, st, wg);
-    if (prec == 2) return serve_slots<2, 1, NW>(code, a, s, slots, dev, st, wg);
-    if (prec == 3) return serve_slots<3, 1, NW>(code, a, s, slots, dev, st, wg);
-    return serve_slots<0, 1, NW>(code, a, s, slots, dev, st, wg);
-  }
-  if (method == 0)  // min-sum: both f64 modes are the same arithmetic
-    return prec == 1 ? serve_slots<1, 0, NW>(code, a, s, slots, dev, st, wg)
-                     : serve_slots<0, 0, NW>(code, a, s, slots, dev, st, wg);
-  return -2;
-}
+// The server's policy over dispatch_small (ldpc_dispatch.hpp): min-sum and
+// sum-product; a decoder workgroup has one wave per slot, and codes that
+// would need workgroups of more than 4 waves go to launches.  No MINB: every
+// cell runs at kServeWavesPerSimd.
+constexpr int kServeSlotsMax = 4;
 
 }  // namespace
 
@@ -503,9 +437,12 @@ int launch_serve(const CodeView &code, const DecodeArgs &a, const ServeArgs &s, 
                  int prec, int slots, int nw, int device, void *stream, int *workgroups_out) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (code.KB > 4 || s.start_epoch >= kServeEpochLimit) return -2;
-  if (nw == 1) return serve_nw<1>(code, a, s, method, prec, slots, device, st, workgroups_out);
-  if (nw == 4) return serve_nw<4>(code, a, s, method, prec, slots, device, st, workgroups_out);
-  return -2;
+  return dispatch_small<kServeSlotsMax>(
+      method, prec, slots, nw, kernel_shape(nw, slots, code.dc_max, code.dv_max), [&](auto cell) {
+        typedef decltype(cell) C;
+        return launch_s<C::PREC, C::METHOD, C::S, C::NW, C::DCN, C::DVN>(code, a, s, device, st,
+                                                                         workgroups_out);
+      });
 }
 
 }  // namespace ldpc

@@ -62,8 +62,10 @@ def threads():
 # ---- the dispatch, restated -------------------------------------------------------
 
 def kernel_shape(M, N, E, dc, dv):
-    """(slots, NW, DCN, DVN, cols) of the small-code kernel: kernel_shape of
-    csrc/ldpc_capi_create.hip and launch_slots of csrc/ldpc_kernels.hip."""
+    """(slots, NW, DCN, DVN, cols) of the small-code kernel: the restatement
+    of kernel_shape in csrc/ldpc_kernels.hpp, the one rule that the layout
+    planner (csrc/ldpc_capi_create.hip) and the launchers' dispatch_small
+    (csrc/ldpc_dispatch.hpp) both go by."""
     S = (E + 63) // 64
     NW = 1 if N <= 64 else 4
     low = NW == 1 and dc <= 6 and dv <= 3 and S <= 4

@@ -39,23 +39,67 @@ def test_restated_dispatch_matches_the_sources():
     """The instantiations the dispatch code names are the cells restated in
     shape_cases: slot counts 1..8 with the generic loops, 1..4 with the low
     ones (dc <= 6, dv <= 3, NW = 1), NW 1 and 4, check bodies 8 / 16 / 32 and
-    variable bodies 4 / 8 / 16."""
+    variable bodies 4 / 8 / 16.  The small-code rule and dispatch have one
+    source each (kernel_shape in ldpc_kernels.hpp, dispatch_small in
+    ldpc_dispatch.hpp), and no launcher states either again."""
+    # the one shape rule, condition by condition
+    hpp = source("ldpc_kernels.hpp")
+    assert "const bool low = nw == 1 && dc_max <= 6 && dv_max <= 3 && slots <= 4;" in hpp
+    assert "const int dcn = low ? 5 : kDcMax - 1, dvn = low ? 3 : kDvMax;" in hpp
+    assert "return KernelShape{low, dcn, dvn, cols_form(1, slots, nw, dvn)};" in hpp
+    assert "return method == 1 && nw == 1 && dvn <= slots;" in hpp
+    frame = source("ldpc_frame.hpp")
+    assert "return cols_form(METHOD, S, NW, DVN);" in frame
+    # ... is stated nowhere else, and the restatement agrees: low cells at 1..4 slots of NW = 1
+    for name in sorted(os.listdir(CSRC)):
+        if os.path.isfile(os.path.join(CSRC, name)) and name != "ldpc_kernels.hpp":
+            t = source(name)
+            assert "dc_max <= 6" not in t and "dv_max <= 3" not in t, name
+            assert "DVN <= S" not in t and "dvn <= slots" not in t, name
+    gen = list(range(1, sc.K_SLOTS_MAX + 1))
+    assert [s for s in gen if sc.kernel_shape(1, 64, 64 * s, 6, 3)[2:4] == (5, 3)] == [1, 2, 3, 4]
+    assert not [s for s in gen if sc.kernel_shape(1, 65, 64 * s, 6, 3)[2:4] == (5, 3)]
+    assert all(sc.kernel_shape(1, 64, 64 * s, dc, dv)[2:4] == (7, 4)
+               for s in gen for dc, dv in ((7, 3), (6, 4)))
+    # the one dispatcher: slots 1..8, a cell instantiated only below the caller's largest
+    # slot count and, for the low loops, only where the rule has a low cell; NW 1 and 4
+    d = source("ldpc_dispatch.hpp")
+    by = d[d.index("int by_slots("):d.index("int by_shape(")]
+    cases = re.findall(r"case (\d): return at\(std::integral_constant<int, (\d)>\{\}\);", by)
+    assert [(int(a), int(b)) for a, b in cases] == [(s, s) for s in gen]
+    assert "if constexpr (S <= MAXS && cell_shape(NW, S, LOW).low == LOW)" in by
+    assert "return f(SmallCell<PREC, METHOD, S, NW, LOW>{});" in by
+    assert "return kernel_shape(nw, slots, low ? 0 : kDcMax, low ? 0 : kDvMax);" in d
+    assert ("static constexpr int DCN = cell_shape(NW, S, LOW).dcn, DVN = cell_shape(NW, S, LOW).dvn;"
+            in d)
+    assert re.findall(r"if \(nw == (\d)\) return dispatch::by_method<MAXS, (\d)>\(", d) == [
+        ("1", "1"), ("4", "4")]
+    # the launchers: each goes through the dispatcher with the code's shape, up to its own
+    # largest slot count (the server's is 4); the multi-wave kernel has 1..8, generic only
+    own = "kernel_shape(nw, slots, code.dc_max, code.dv_max)"
     k = source("ldpc_kernels.hip")
-    body = k[k.index("static int launch_slots"):k.index("static int launch_nw")]
-    low = sorted(int(s) for s in re.findall(r"launch_one<PREC, METHOD, (\d), NW, 5, 3>", body))
-    gen = sorted(int(s) for s in re.findall(r"launch_one<PREC, METHOD, (\d), NW>", body))
-    assert low == [1, 2, 3, 4] and gen == list(range(1, sc.K_SLOTS_MAX + 1))
-    assert "code.dc_max <= 6 && code.dv_max <= 3" in body and "NW == 1 && METHOD <= 1" in body
-    mw = k[k.index("static int launch_mw_slots"):k.index("static int launch_slots")]
-    assert sorted(int(s) for s in re.findall(r"launch_mw<PREC, METHOD, (\d), NW>", mw)) == gen
-    assert re.findall(r"launch_nw<(\d)>\(code", k) == ["1", "4"]
+    assert "constexpr int kBatchSlotsMax = kSlotsMax;" in k
+    calls = re.findall(r"dispatch_small<kBatchSlotsMax>\(method, prec, slots, nw,\s*([^;]*?),\s*"
+                       r"(Launch\w+)\{code, a, st\}\);", k)
+    assert calls == [("kernel_shape(nw, slots, kDcMax, kDvMax)", "LaunchMw"), (own, "LaunchOne")]
+    assert "return launch_mw<C::PREC, C::METHOD, C::S, C::NW>(code, a, st);" in k
+    assert k.count("launch_one<C::PREC, C::METHOD, C::S, C::NW, C::DCN, C::DVN, ") == 2
+    ring = source("ldpc_ring.hip")
+    assert "constexpr int kRingSlotsMax = kSlotsMax;" in ring
+    assert re.search(r"dispatch_small<kRingSlotsMax>\(\s*method, prec, slots, nw, %s," % re.escape(own),
+                     ring)
+    assert "launch_r<C::PREC, C::METHOD, C::S, C::NW, C::DCN, C::DVN, ring_minb<C>()>(" in ring
+    serve = source("ldpc_serve.hip")
+    assert constant(serve, "kServeSlotsMax") == 4
+    assert re.search(r"dispatch_small<kServeSlotsMax>\(\s*method, prec, slots, nw, %s," % re.escape(own),
+                     serve)
+    assert "launch_s<C::PREC, C::METHOD, C::S, C::NW, C::DCN, C::DVN>(" in serve
     capi = source("ldpc_capi_create.hip")
-    assert "nw == 1 && dc_max <= 6 && dv_max <= 3 && slots <= 4" in capi
+    assert "ldpc::kernel_shape(nw, slots, code.dc_max, code.dv_max);" in capi
+    assert "slots, nw, shape.dcn, shape.dvn,\n" in capi and "shape.cols, search);" in capi
     assert "ctx->nw = N <= 64 ? 1 : 4;" in capi
-    for name in ("ldpc_ring.hip", "ldpc_serve.hip"):
-        t = source(name)
-        assert "code.dc_max <= 6 && code.dv_max <= 3" in t, name
-        assert "constexpr int D = kDcMax - 1, V = kDvMax;" in t, name
+    assert sum(source(n).count("#define LDPC_TP_MINB") for n in os.listdir(CSRC)
+               if os.path.isfile(os.path.join(CSRC, n))) == 1
     g = source("ldpc_graph.hip")
     assert sorted(set(int(d) for d in re.findall(r"g_check<PREC, (\d+)><<<", g))) == [8, 16, 32]
     assert sorted(set(int(d) for d in re.findall(r"g_var<Real, (\d+)><<<", g))) == [4, 8, 16]
