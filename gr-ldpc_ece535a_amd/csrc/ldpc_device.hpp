@@ -21,7 +21,13 @@ namespace ldpc {
 //               reciprocal): an independent evaluation of mode 0
 //   3 F64_FAST  double, compact approximations (ldpc_math.hpp): tanh within
 //               3 ulp of glibc, table log within 1 ulp -- faster, not exact
-//   1 F32       float, ROCm libm
+//   1 F32       float.  Min-sum uses abs_ / max_ alone, never tanh or log:
+//               it is the reference's arithmetic in float and is held bit for
+//               bit to the oracle's float restatement
+//               (tests/test_gpu_minsum_f32.py).  Sum-product uses ROCm's
+//               tanhf / logf and, like mode 3 (whose compact forms start from
+//               the device's reciprocal seed), has no oracle: neither can be
+//               restated bit for bit on a host
 // tanh_half(m) = tanh(m / 2) (:509); check_msg(T, tab) = log((1+T)/(1-T))
 // (:513); the _n forms take n independent operands (a lane's edge slots /
 // column entries) so their divisions can share one reciprocal.  `Tab` is

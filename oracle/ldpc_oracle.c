@@ -703,6 +703,129 @@ int orc_decode_batch_sparse_et(int method, const int32_t *row_ptr, const int32_t
 }
 
 /* ------------------------------------------------------------------ */
+/* min-sum in float (the contract of the decoder's LDPC_PREC_F32 min-sum) */
+/* ------------------------------------------------------------------ */
+static int orc_signf(float v) { return (v > 0) - (v < 0); }
+
+/* orc_minsum_sparse with `float` where it has `double`: every operation
+ * below is one IEEE single-precision operation (x86-64 evaluates float
+ * expressions in float; -ffp-contract=off keeps them apart).  tx is the float
+ * product re * polarity, negated as an operation of its own. */
+static int orc_minsum_sparse_f32(const orc_graph *g, const float *tx, int iterations, int et,
+                                 int *vhat, float *post_opt) {
+  const int N = g->N, M = g->M, E = g->E;
+  float *Lci = (float *)malloc(sizeof(float) * N);
+  float *Lq = (float *)malloc(sizeof(float) * (size_t)(E > 0 ? E : 1));
+  float *Lr = (float *)calloc((size_t)(E > 0 ? E : 1), sizeof(float));
+  for (int i = 0; i < N; i++) Lci[i] = -tx[i];
+  for (int e = 0; e < E; e++) Lq[e] = Lci[g->ci[e]];
+  for (int i = 0; i < N; i++) vhat[i] = 0;
+  int used = iterations;
+  for (int it = 0; it < iterations; it++) {
+    for (int r = 0; r < M; r++) { /* horizontal step, :350-376 */
+      int sgn = 1;
+      for (int e = g->rp[r]; e < g->rp[r + 1]; e++) sgn *= orc_signf(Lq[e]);
+      for (int e = g->rp[r]; e < g->rp[r + 1]; e++) {
+        float lo = FLT_MAX;
+        for (int k = g->rp[r]; k < g->rp[r + 1]; k++)
+          if (k != e && fabsf(Lq[k]) < lo) lo = fabsf(Lq[k]);
+        Lr[e] = (float)(sgn * orc_signf(Lq[e])) * lo;
+      }
+    }
+    for (int c = 0; c < N; c++) { /* vertical step, :379-403 */
+      float s = 0.0f;
+      for (int k = g->cp[c]; k < g->cp[c + 1]; k++) s += Lr[g->ce[k]];
+      const float LQ = Lci[c] + s;
+      for (int k = g->cp[c]; k < g->cp[c + 1]; k++) {
+        const int e = g->ce[k];
+        Lq[e] = LQ - Lr[e];
+      }
+      vhat[c] = (LQ < 0) ? 1 : 0;
+      if (post_opt) post_opt[c] = LQ;
+    }
+    if (it + 1 < iterations && ET_DUE(it, et) &&
+        orc_check_frame_sparse(g->rp, g->ci, M, vhat, 0) == 0) {
+      used = it + 1;
+      break;
+    }
+  }
+  free(Lci);
+  free(Lq);
+  free(Lr);
+  return used;
+}
+
+typedef struct {
+  int M, N, iterations, et, B, stride_threads, first;
+  const orc_graph *g;
+  const float *in;
+  long cw_stride;
+  int elem_stride;
+  float polarity;
+  uint8_t *bits, *packed;
+  int32_t *iters, *synd;
+  float *post;
+} orc_f32_job;
+
+static void *orc_f32_worker(void *arg) {
+  orc_f32_job *jb = (orc_f32_job *)arg;
+  const int N = jb->N, M = jb->M, K = N - M, KB = (K + 7) / 8;
+  float *tx = (float *)malloc(sizeof(float) * N);
+  int *v = (int *)malloc(sizeof(int) * N);
+  for (int b = jb->first; b < jb->B; b += jb->stride_threads) {
+    const float *src = jb->in + (long)b * jb->cw_stride;
+    for (int i = 0; i < N; i++) tx[i] = src[(long)i * jb->elem_stride] * jb->polarity;
+    const int used = orc_minsum_sparse_f32(jb->g, tx, jb->iterations, jb->et, v,
+                                           jb->post ? jb->post + (long)b * N : NULL);
+    if (jb->iters) jb->iters[b] = used;
+    if (jb->synd) jb->synd[b] = orc_check_frame_sparse(jb->g->rp, jb->g->ci, M, v, M);
+    if (jb->bits)
+      for (int i = 0; i < N; i++) jb->bits[(long)b * N + i] = (uint8_t)v[i];
+    if (jb->packed)
+      for (int q = 0; q < KB; q++) {
+        uint8_t o = 0;
+        for (int j = 0; j < 8; j++) {
+          const int c = M + q * 8 + j;
+          if (c < N && v[c] == 1) o |= (uint8_t)(1u << (7 - j));
+        }
+        jb->packed[(long)b * KB + q] = o;
+      }
+  }
+  free(tx);
+  free(v);
+  return NULL;
+}
+
+int orc_minsum_f32_batch_sparse_et(const int32_t *row_ptr, const int32_t *col_idx, int M, int N,
+                                   int iterations, int et_period, const float *in,
+                                   long cw_stride, int elem_stride, float polarity, int B,
+                                   uint8_t *bits_opt, uint8_t *packed_opt, int32_t *iters_opt,
+                                   int32_t *synd_opt, float *post_opt, int nthreads) {
+  if (et_period < 1) et_period = 1;
+  orc_graph g;
+  orc_graph_build(&g, row_ptr, col_idx, M, N);
+  if (nthreads < 1) nthreads = 1;
+  if (nthreads > B) nthreads = B > 0 ? B : 1;
+  orc_f32_job *jobs = (orc_f32_job *)malloc(sizeof(orc_f32_job) * (size_t)nthreads);
+  pthread_t *tids = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)nthreads);
+  for (int t = 0; t < nthreads; t++) {
+    orc_f32_job j = {M, N, iterations, et_period, B, nthreads, t, &g, in, cw_stride,
+                     elem_stride, polarity, bits_opt, packed_opt, iters_opt, synd_opt, post_opt};
+    jobs[t] = j;
+  }
+  if (nthreads == 1) {
+    orc_f32_worker(&jobs[0]);
+  } else {
+    for (int t = 0; t < nthreads; t++) pthread_create(&tids[t], NULL, orc_f32_worker, &jobs[t]);
+    for (int t = 0; t < nthreads; t++) pthread_join(tids[t], NULL);
+  }
+  free(jobs);
+  free(tids);
+  orc_graph_free(&g);
+  return 0;
+}
+
+/* ------------------------------------------------------------------ */
 /* general_work -- lib/ldpc_decoder_cb_impl.cc:133-234                  */
 /* ------------------------------------------------------------------ */
 void orc_block_init(orc_block *blk, int method, int iterations,

@@ -115,6 +115,20 @@ int orc_decode_batch_sparse_et(int method, const int32_t *row_ptr, const int32_t
                                uint8_t *bits_opt, uint8_t *packed_opt, int32_t *iters_opt,
                                int32_t *synd_opt, int nthreads);
 
+/* Min-sum (decodeLogDomainSimple, :309-412) restated with `float` where the
+ * reference has `double`: the contract of the decoder's f32 min-sum, which
+ * is the same template at Real = float.  Lci = -tx with tx = in * polarity
+ * the float product; FLT_MAX seeds the minimum; s starts at 0.0f and takes the
+ * column's check messages in ascending row; Lq = (Lci + s) - Lr; the
+ * posterior Lci + s is returned as the float itself; vhat = LQ < 0; the early
+ * exit and et_period are orc_decode_batch_sparse_et's.  Same layout of inputs
+ * and outputs, plus post_opt (B x N floats, optional). */
+int orc_minsum_f32_batch_sparse_et(const int32_t *row_ptr, const int32_t *col_idx, int M, int N,
+                                   int iterations, int et_period, const float *in,
+                                   long cw_stride, int elem_stride, float polarity, int B,
+                                   uint8_t *bits_opt, uint8_t *packed_opt, int32_t *iters_opt,
+                                   int32_t *synd_opt, float *post_opt, int nthreads);
+
 /* general_work restatement, lib/ldpc_decoder_cb_impl.cc:133-234 + forecast
  * :126-130.  `in` is interleaved gr_complex (re, im).  State lives in the
  * struct (d_state, d_errors); the block's constants are d_M, d_N from H. */

@@ -59,6 +59,12 @@ def lib():
                                               ctypes.c_int, ctypes.c_float, ctypes.c_int, _u8p,
                                               _u8p, _i32p, _i32p, ctypes.c_int]
         L.orc_decode_batch_sparse.restype = ctypes.c_int
+        L.orc_minsum_f32_batch_sparse_et.argtypes = [_i32p, _i32p, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_int, ctypes.c_int, _f32p,
+                                                     ctypes.c_long, ctypes.c_int, ctypes.c_float,
+                                                     ctypes.c_int, _u8p, _u8p, _i32p, _i32p,
+                                                     _f32p, ctypes.c_int]
+        L.orc_minsum_f32_batch_sparse_et.restype = ctypes.c_int
         L.orc_block_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _u8p,
                                      ctypes.c_int, ctypes.c_int]
         L.orc_block_init.restype = None
@@ -127,13 +133,30 @@ def decode_one(method, Hr, rx, iterations):
     return v, used, post
 
 
+def _real(real, method):
+    if real not in ("f64", "f32"):
+        raise ValueError("real must be 'f64' or 'f32', not %r" % (real,))
+    if real == "f32" and int(method) != 0:
+        raise ValueError("the float oracle restates min-sum (method 0) only, not method %r"
+                         % (method,))
+    return real == "f32"
+
+
 def decode_batch(method, Hr, llr, iterations, polarity=1.0, nthreads=1, cw_stride=None,
-                 elem_stride=1, B=None, want_post=False, et_period=1):
+                 elem_stride=1, B=None, want_post=False, et_period=1, real="f64"):
     """Decode B frames of float32 samples.  Returns dict with bits (B,N) u8,
     packed (B,KB) u8, iters (B,) i32, synd (B,) i32 [, post (B,N) f32].
-    et_period > 1 thins the early-exit test (orc_decode_et; 1 = reference)."""
+    et_period > 1 thins the early-exit test (orc_decode_et; 1 = reference).
+    real="f32": min-sum in float arithmetic (method 0 only), through the
+    sparse restatement, which adds the same terms in the same order."""
     Hr = np.ascontiguousarray(Hr, np.uint8)
     M, N = Hr.shape
+    if _real(real, method):
+        rp, ci = dense_to_csr(Hr)
+        return decode_batch_sparse(0, rp, ci, M, N, llr, iterations, polarity=polarity,
+                                   nthreads=nthreads, cw_stride=cw_stride,
+                                   elem_stride=elem_stride, B=B, et_period=et_period,
+                                   real="f32", want_post=want_post)
     llr = np.ascontiguousarray(llr, np.float32)
     if cw_stride is None:
         cw_stride = N * elem_stride
@@ -157,8 +180,13 @@ def decode_batch(method, Hr, llr, iterations, polarity=1.0, nthreads=1, cw_strid
 
 def decode_batch_sparse(method, row_ptr, col_idx, M, N, llr, iterations, polarity=1.0,
                         nthreads=1, cw_stride=None, elem_stride=1, B=None, want_bits=True,
-                        et_period=1):
-    """Sparse (CSR) restatement for large codes; same outputs as decode_batch."""
+                        et_period=1, real="f64", want_post=False):
+    """Sparse (CSR) restatement for large codes; same outputs as decode_batch.
+    real="f32": min-sum in float arithmetic (method 0 only); want_post then
+    adds post (B,N) f32, the float posteriors themselves."""
+    f32 = _real(real, method)
+    if want_post and not f32:
+        raise ValueError("the sparse f64 restatement returns no posteriors")
     rp = np.ascontiguousarray(row_ptr, np.int32)
     ci = np.ascontiguousarray(col_idx, np.int32)
     llr = np.ascontiguousarray(llr, np.float32)
@@ -171,14 +199,25 @@ def decode_batch_sparse(method, row_ptr, col_idx, M, N, llr, iterations, polarit
     packed = np.zeros((B, KB), np.uint8)
     iters = np.zeros(B, np.int32)
     synd = np.zeros(B, np.int32)
-    lib().orc_decode_batch_sparse_et(int(method), _p(rp, _i32p), _p(ci, _i32p), int(M), int(N),
-                                     int(iterations), int(et_period), _p(llr, _f32p),
-                                     int(cw_stride), int(elem_stride), float(polarity), int(B),
-                                     _p(bits, _u8p), _p(packed, _u8p), _p(iters, _i32p),
-                                     _p(synd, _i32p), int(nthreads))
+    if f32:
+        post = np.zeros((B, N), np.float32) if want_post else None
+        lib().orc_minsum_f32_batch_sparse_et(_p(rp, _i32p), _p(ci, _i32p), int(M), int(N),
+                                             int(iterations), int(et_period), _p(llr, _f32p),
+                                             int(cw_stride), int(elem_stride), float(polarity),
+                                             int(B), _p(bits, _u8p), _p(packed, _u8p),
+                                             _p(iters, _i32p), _p(synd, _i32p), _p(post, _f32p),
+                                             int(nthreads))
+    else:
+        lib().orc_decode_batch_sparse_et(int(method), _p(rp, _i32p), _p(ci, _i32p), int(M), int(N),
+                                         int(iterations), int(et_period), _p(llr, _f32p),
+                                         int(cw_stride), int(elem_stride), float(polarity), int(B),
+                                         _p(bits, _u8p), _p(packed, _u8p), _p(iters, _i32p),
+                                         _p(synd, _i32p), int(nthreads))
     out = dict(packed=packed, iters=iters, synd=synd)
     if want_bits:
         out["bits"] = bits
+    if f32 and want_post:
+        out["post"] = post
     return out
 
 

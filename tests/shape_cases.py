@@ -230,6 +230,16 @@ class Case:
             self._refs[key] = self._oracle(method, y, cap, et)
         return self._refs[key]
 
+    def ref_f32(self, cap=CAP, et=1):
+        """The float oracle's min-sum on the case's frames (posteriors
+        included): the contract of precision 1, method 0."""
+        key = ("f32", cap, et)
+        if key not in self._refs:
+            from oracle import oracle as orc
+            self._refs[key] = orc.decode_batch(0, self.H, self.frames, cap, nthreads=threads(),
+                                               want_post=True, et_period=et, real="f32")
+        return self._refs[key]
+
     def ref_for(self, tag, method, y, cap=CAP):
         """The oracle's result on other frames of this case, cached under tag."""
         key = (tag, method, cap)

@@ -142,21 +142,22 @@ def test_dvbs2_like_other_methods_vs_sparse_oracle(dvb, method, prec):
 
 def test_dvbs2_like_full_batch_roundtrip(dvb):
     """Config-4 batch (1024 frames at 2 dB): every frame decodes to its info
-    bits with a zero syndrome, f64 and f32; all 1024 f64 frames (packed
-    bytes, iterations, syndromes) equal the sparse oracle's."""
+    bits with a zero syndrome, f64 and f32; all 1024 frames (packed bytes,
+    iterations, syndromes) equal the sparse oracle's: the double one at f64,
+    its float restatement at f32."""
     csr, d = dvb
     M, N, rp, ci = csr
     info, y = _noisy(csr, 1024, 2, seed=4)
     want = np.packbits(info, axis=1)
     from oracle import oracle as orc
-    ref = orc.decode_batch_sparse(0, rp, ci, M, N, y, 50, nthreads=16, want_bits=False)
-    for prec in (0, 1):
+    for prec, real in ((0, "f64"), (1, "f32")):
+        ref = orc.decode_batch_sparse(0, rp, ci, M, N, y, 50, nthreads=16, want_bits=False,
+                                      real=real)
         out = d.decode(y, method=0, max_iters=50, precision=prec, want_bits=False)
         assert (out["synd"] == 0).all()
         assert (out["packed"] == want).all()
-        if prec == 0:
-            for k in ("packed", "iters", "synd"):
-                np.testing.assert_array_equal(out[k], ref[k], err_msg=k)
+        for k in ("packed", "iters", "synd"):
+            np.testing.assert_array_equal(out[k], ref[k], err_msg="%s %s" % (k, real))
 
 
 @pytest.mark.parametrize("method,db,compact", [(0, 2, "1"), (1, 2, "1"), (0, 4, "1"), (1, 1, "1"),

@@ -163,8 +163,9 @@ def test_high_check_degree_vs_sparse_oracle(hi_groups, hi_deg, dc):
     whose rows have 13-14 and 19-20 edges: the narrow pipeline's check pass
     then runs its 16- and 32-slot bodies with the slots past each block's
     degree masked, and its variable pass the degree-12 columns; every f64
-    output equals the sparse oracle's, at an Eb/N0 beyond the code's reach
-    and at one within it."""
+    output equals the sparse oracle's and every f32 output (posteriors as bit
+    patterns included) its float restatement's, at an Eb/N0 beyond the code's
+    reach and at one within it."""
     from ldpc_ece535a import codes
     from oracle import oracle as orc
     table = codes.dvbs2_like_table(3, K=5400, N=7200, hi_groups=hi_groups, hi_deg=hi_deg,
@@ -183,7 +184,13 @@ def test_high_check_degree_vs_sparse_oracle(hi_groups, hi_deg, dc):
         ref = orc.decode_batch_sparse(0, rp, ci, M, N, y, 40, nthreads=16)
         for k in ("bits", "packed", "iters", "synd"):
             np.testing.assert_array_equal(out[k], ref[k], err_msg="%s %g dB" % (k, db))
-    # f32: decisions only (6 dB: most frames decode)
+        # f32: the same arithmetic in float, all frames
+        out = d.decode(y, method=0, max_iters=40, precision=1, want_llr=True)
+        ref32 = orc.decode_batch_sparse(0, rp, ci, M, N, y, 40, nthreads=16, real="f32",
+                                        want_post=True)
+        for k in ("bits", "packed", "iters", "synd"):
+            np.testing.assert_array_equal(out[k], ref32[k], err_msg="f32 %s %g dB" % (k, db))
+        np.testing.assert_array_equal(out["llr"].view(np.uint32), ref32["post"].view(np.uint32))
+    # 6 dB: most frames decode, in either arithmetic
     assert (ref["synd"] == 0).mean() > 0.5
-    out = d.decode(y, method=0, max_iters=40, precision=1)
     assert ((out["packed"] == np.packbits(info, axis=1)).all(axis=1)).mean() > 0.5

@@ -331,16 +331,30 @@ def test_ring_and_server_are_refused(c720):
 @pytest.mark.parametrize("prec", [1, 3])
 @pytest.mark.parametrize("method", [0, 1])
 def test_inexact_modes_equal_large_code_path(odec, golden, method, prec):
-    """Precisions 1 (f32) and 3 (compact f64) have no oracle; the large-code
-    kernels evaluate the same scalar Math<PREC> calls in the same order with
-    contraction off, so every output is equal, posteriors bit for bit."""
+    """Sum-product at precisions 1 (f32) and 3 (compact f64) has no oracle;
+    the large-code kernels evaluate the same scalar Math<PREC> calls in the
+    same order with contraction off, so every output is equal, posteriors bit
+    for bit.  Min-sum has one at either precision: the oracle's float
+    restatement at f32, the oracle itself (its fixtures) at the compact f64
+    mode, which for min-sum is plain double arithmetic."""
     import ldpc_ece535a as L
+    from oracle import oracle as orc
     fd = golden("frames_default.npz")
     g = L.Decoder(force_graph=True)
     for db in (0, 2, 4):
         for iters in (5, 50):
+            what = "db %d iters %d" % (db, iters)
             kw = dict(method=method, max_iters=iters, precision=prec, want_llr=True)
             a = odec.decode(fd["db%d_llr" % db], **kw)
             b = g.decode(fd["db%d_llr" % db], **kw)
-            _eq(a, b, what="db %d iters %d" % (db, iters))
-            _same_bits(a["llr"], b["llr"], what="db %d iters %d" % (db, iters))
+            _eq(a, b, what=what)
+            _same_bits(a["llr"], b["llr"], what=what)
+            if method == 0:
+                if prec == 1:
+                    ref = orc.decode_batch(0, fd["H_reordered"], fd["db%d_llr" % db], iters,
+                                           want_post=True, real="f32")
+                else:
+                    key = "db%d_m0_i%d_" % (db, iters)
+                    ref = {k: fd[key + k] for k in KEYS + ("post",)}
+                _eq(a, ref, what=what + ", on-chip vs oracle")
+                _same_bits(a["llr"], ref["post"], what=what + ", on-chip vs oracle")

@@ -7,8 +7,10 @@ on the launch path (every method, both exact precisions, both schedules),
 forced onto the large-code and on-chip kernels, through the device entry
 point into guarded buffers, the frame ring and the window server, and
 compared with the oracle's decode of the same frames: bits, packed bytes,
-iteration counts, syndrome weights, and posteriors as bit patterns.  The fast
-modes, which have no oracle, are held to what no rounding can change."""
+iteration counts, syndrome weights, and posteriors as bit patterns.  Of the
+fast modes, min-sum is exact too (at f32 the oracle's float restatement, at
+the compact f64 mode the oracle itself); fast sum-product, which has no
+oracle, is held to what no rounding can change."""
 import numpy as np
 import pytest
 
@@ -307,11 +309,17 @@ def test_window_server_refuses_eight_slots(ctx):
 @pytest.mark.parametrize("method", [0, 1])
 @cases(SMALL + LARGE)
 def test_fast_modes(ctx, method, prec):
-    """Precisions 1 (f32) and 3 (compact f64) have no oracle.  Whatever the
-    rounding: the noise-free frame decodes in one iteration to a zero
-    syndrome and the oracle's bits (zero on every column that has a check),
-    frames the oracle decodes within 5 iterations get the oracle's decisions,
-    and the planned and the plain layout give equal outputs bit for bit."""
+    """Sum-product at precisions 1 (f32: ROCm's tanhf / logf) and 3 (compact
+    f64: the device's reciprocal seed) has no oracle: neither can be restated
+    bit for bit on a host.  Whatever the rounding: the noise-free frame
+    decodes in one iteration to a zero syndrome and the oracle's bits (zero
+    on every column that has a check), frames the oracle decodes within 5
+    iterations get the oracle's decisions, and the planned and the plain
+    layout give equal outputs bit for bit.  Min-sum has neither function: at
+    precision 1 it is the reference's arithmetic in float and equals the
+    oracle's float restatement on all frames, at precision 3 it is double
+    arithmetic and equals the oracle itself, posteriors as bit patterns
+    included."""
     c = ctx.case
     dec = ctx.dec()
     N = c.H.shape[1]
@@ -330,6 +338,8 @@ def test_fast_modes(ctx, method, prec):
         out = dec.decode(c.frames, method=method, max_iters=CAP, precision=prec, want_llr=True)
         np.testing.assert_array_equal(out["bits"][easy], ref["bits"][easy], err_msg=what)
         np.testing.assert_array_equal(out["packed"][easy], ref["packed"][easy], err_msg=what)
+        if method == 0:
+            check(out, c.ref_f32() if prec == 1 else ref, what + ", all frames")
         if c.small:
             plain = ctx.dec("plain")
             plain.set_schedule(sched)
