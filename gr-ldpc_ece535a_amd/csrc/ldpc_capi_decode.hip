@@ -386,13 +386,7 @@ int decode_device_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, 
   }
   a.pm_half = pm_half;
   size_t q = 0;
-  if ((rc = stream_queue(ctx, st, q)) != LDPC_OK) return rc;
-  a.ticket = ctx->queues.d_tickets + q * kTicketStride;
-  a.ticket_base = ctx->queues.list[q].base;
-  a.waves = 0;
-  // short frames (iteration cap <= 10): fixed frame stride, no queue atomics
-  // (ldpc_kernels.hpp DecodeArgs::static_stride)
-  a.static_stride = max_iters <= 10 ? 1 : 0;
+  if ((rc = bind_queue(ctx, st, max_iters, a, q)) != LDPC_OK) return rc;
   a.fair_cycles = ctx->small.fair_cycles;
   uint32_t advance = 0;
   if (onchip)
@@ -403,7 +397,7 @@ int decode_device_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, 
                              ctx->small.waves_per_cu, ctx->small.schedule, st, &advance);
   if (rc == -2) return set_err(ctx, LDPC_EUNSUPPORTED, "no kernel for this code shape");
   if (rc != 0) return hip_err(ctx, hipGetLastError(), "kernel launch");
-  ctx->queues.list[q].base += advance;  // what the launch adds to its counter (B with one frame per claim)
+  commit_queue(ctx, q, advance);  // B with one frame per claim
   return LDPC_OK;
 }
 

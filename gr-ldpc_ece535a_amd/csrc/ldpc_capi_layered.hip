@@ -260,11 +260,7 @@ int layered_device_impl(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_ite
   if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
   void *st = hip_stream ? hip_stream : (void *)ctx->stream;
   size_t q = 0;
-  if ((rc = stream_queue(ctx, st, q)) != LDPC_OK) return rc;
-  a.ticket = ctx->queues.d_tickets + q * kTicketStride;
-  a.ticket_base = ctx->queues.list[q].base;
-  a.waves = 0;
-  a.static_stride = max_iters <= 10 ? 1 : 0;
+  if ((rc = bind_queue(ctx, st, max_iters, a, q)) != LDPC_OK) return rc;
   uint32_t advance = 0;
   int launched;
   if (ly.qc) {
@@ -292,7 +288,7 @@ int layered_device_impl(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_ite
     launched = ldpc::launch_layered_decode(v, a, lay, ar, st, resident, &advance);
   }
   if (launched != 0) return hip_err(ctx, hipGetLastError(), "kernel launch");
-  ctx->queues.list[q].base += advance;
+  commit_queue(ctx, q, advance);
   return LDPC_OK;
 }
 

@@ -53,6 +53,28 @@ int stream_queue(ldpc_ctx *ctx, void *st, size_t &q) {
   return LDPC_OK;
 }
 
+// The host's half of the frame-queue protocol (ldpc_kernels.hpp
+// DecodeArgs::ticket; the device's: ldpc_wgframe.hpp wg_next_frame and the
+// small-code kernels' claims).  The counter only grows, and base is its value
+// when the next launch on the stream starts: a launch whose frame indices are
+// counter - base stays below B only if every launch before it was committed
+// with exactly what it added.
+int bind_queue(ldpc_ctx *ctx, void *st, int max_iters, ldpc::DecodeArgs &a, size_t &q) {
+  const int rc = stream_queue(ctx, st, q);
+  if (rc != LDPC_OK) return rc;
+  a.ticket = ctx->queues.d_tickets + q * kTicketStride;
+  a.ticket_base = ctx->queues.list[q].base;
+  a.waves = 0;  // the launcher's
+  // short frames (iteration cap <= 10): fixed frame stride, no queue atomics
+  // (DecodeArgs::static_stride)
+  a.static_stride = max_iters <= 10 ? 1 : 0;
+  return LDPC_OK;
+}
+
+void commit_queue(ldpc_ctx *ctx, size_t q, uint32_t advance) {
+  ctx->queues.list[q].base += advance;
+}
+
 }  // namespace capi
 }  // namespace ldpc
 

@@ -356,6 +356,12 @@ bool ensure_tickets(ldpc_ctx *ctx, const char *&failed, hipError_t &e);
 // The frame-queue counter of stream `st` on this context: q is its slot in
 // ctx->queues.list / ctx->queues.d_tickets.
 int stream_queue(ldpc_ctx *ctx, void *st, size_t &q);
+// Binds a launch to stream `st`'s queue: a.ticket, ticket_base, static_stride
+// (a fixed stride for iteration caps <= 10) and waves = 0; q as stream_queue's.
+int bind_queue(ldpc_ctx *ctx, void *st, int max_iters, ldpc::DecodeArgs &a, size_t &q);
+// After the launch was enqueued: `advance` is what it adds to the counter
+// (the launcher's *advance_out; 0 with a fixed stride).
+void commit_queue(ldpc_ctx *ctx, size_t q, uint32_t advance);
 
 // ---- ldpc_capi_decode.hip ----
 int check_decode_args(ldpc_ctx *ctx, int &method, int max_iters, int et_period, int precision,

@@ -2,7 +2,9 @@
 // small-code kernels (ldpc_kernels.hip, ldpc_ring.hip, ldpc_serve.hip): the
 // one runtime-to-template dispatch, and the per-device / per-kernel figures a
 // launch is sized with.  Each launcher keeps what is its own: the launch, its
-// largest slot count and its MINB policy.
+// largest slot count and its MINB policy.  The launchers of the
+// workgroup-per-frame kernels (ldpc_onchip.hip, ldpc_layered.hip) size theirs
+// with resident_workgroups / wg_launch at the end of this file.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -109,6 +111,29 @@ int cu_count(int dev);
 // racing threads compute the same value).  Raises the kernel's dynamic-LDS
 // limit first when lds > 64 KiB.  0: that failed.
 int resident_per_cu(std::atomic<int> &once, const void *fn, int threads, size_t lds, int cap);
+
+// Workgroups the current device holds of kernel `fn` at `threads` threads and
+// `lds` bytes of dynamic LDS, for the workgroup-per-frame kernels
+// (ldpc_onchip.hip, ldpc_layered.hip): computed when `cache` is 0 and kept
+// there.  The LDS size is the code's, so the cache is the context's
+// (ldpc_ctx::Onchip::resident, Layered::resident, q8_resident), reset with the
+// layout -- resident_per_cu's one word per kernel instantiation would hand one
+// code's figure to another.  The kernel's dynamic-LDS limit is raised to
+// `lds_limit` first: the attribute belongs to the kernel, not to this code, so
+// it allows any layout the planner accepts.  False on a runtime error of the
+// attribute or the occupancy query; the CU count is cu_count's, 256 where the
+// device does not answer (more workgroups than it holds then queue up behind
+// each other: none waits on another).
+bool resident_workgroups(const void *fn, int threads, int lds, int lds_limit, int &cache);
+
+// The shape of one workgroup-per-frame launch, the host's half of
+// wg_next_frame (ldpc_wgframe.hpp): a.waves, the resident workgroups or one per
+// frame of a smaller batch, and *advance_out, what the launch adds to its
+// queue counter -- one add per frame decoded, each workgroup's last being the
+// one past the batch, so a.B; 0 with a fixed stride.  False when
+// resident_workgroups fails.
+bool wg_launch(const void *fn, int threads, int lds, int &cache, DecodeArgs &a,
+               uint32_t *advance_out);
 
 }  // namespace ldpc
 

@@ -13,6 +13,7 @@
 #include "ldpc_device.hpp"
 #include "ldpc_kernels.hpp"
 #include "ldpc_layout.hpp"
+#include "ldpc_wgframe.hpp"  // frame_src
 
 namespace ldpc {
 
@@ -856,22 +857,6 @@ __device__ __forceinline__ FrameResult decode_samples(const CodeView &code, cons
         code, a, b, wt, tb, eb, rb, sb, lane, logtab, xin, colq, ppos);
   }
   return fr;
-}
-
-// Frame b's first sample and polarity (DecodeArgs::pm_half: the second half
-// of a both-polarities launch re-reads the first half's windows negated).
-__device__ __forceinline__ const float *frame_src(const DecodeArgs &a, int64_t b, float &pol) {
-  if (a.win) {
-    const int64_t w = a.win[b];
-    pol = (w & 1) ? -a.polarity : a.polarity;
-    return a.in + (w >> 1) * a.elem_stride;
-  }
-  pol = a.polarity;
-  if (a.pm_half > 0 && b >= a.pm_half) {
-    b -= a.pm_half;
-    pol = -pol;
-  }
-  return a.in + b * a.cw_stride;
 }
 
 // Per-wave setup of the small-code kernels: the code's tables into registers

@@ -49,6 +49,7 @@
 
 #include "ldpc_device.hpp"
 #include "ldpc_graph.hpp"
+#include "ldpc_wgframe.hpp"  // lci_of
 
 namespace ldpc {
 namespace {
@@ -658,13 +659,8 @@ __global__ void __launch_bounds__(256, LDPC_MSN_VAR_MINB) msn_var(MsnView g, Msn
     const int64_t src = (int64_t)g.corig[x] * a.elem_stride;
 #pragma unroll
     for (int f = 0; f < kF; ++f)
-      if ((fill >> f) & 1u) {
-        // two operations, as in the reference: folded into one multiply by
-        // -polarity, a NaN sample would keep the sign that negating tx flips
-        float tx = a.in[(int64_t)w.frame[k * kF + f] * a.cw_stride + src] * a.polarity;
-        asm volatile("" : "+v"(tx));
-        lci.v[f] = -tx;
-      }
+      if ((fill >> f) & 1u)
+        lci.v[f] = lci_of(a.in[(int64_t)w.frame[k * kF + f] * a.cw_stride + src], a.polarity);
     stv(w.L + ci, lci);
   }
   Vec<Real> s;

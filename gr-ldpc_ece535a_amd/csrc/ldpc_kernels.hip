@@ -405,6 +405,25 @@ int resident_per_cu(std::atomic<int> &once, const void *fn, int threads, size_t 
   return per_cu;
 }
 
+bool resident_workgroups(const void *fn, int threads, int lds, int lds_limit, int &cache) {
+  if (cache != 0) return true;
+  int per_cu = 0, dev = 0;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, (size_t)lds) != hipSuccess ||
+      per_cu < 1 || hipGetDevice(&dev) != hipSuccess)
+    return false;
+  cache = per_cu * cu_count(dev);
+  return true;
+}
+
+bool wg_launch(const void *fn, int threads, int lds, int &cache, DecodeArgs &a,
+               uint32_t *advance_out) {
+  if (!resident_workgroups(fn, threads, lds, kWgLdsLimit, cache)) return false;
+  a.waves = (int)std::min<int64_t>(a.B, cache);
+  *advance_out = a.static_stride ? 0u : (uint32_t)a.B;
+  return true;
+}
+
 int launch_decode(const CodeView &code, const DecodeArgs &args, int method, int prec, int slots,
                   int nw, int waves_per_cu, int schedule, void *stream, uint32_t *advance_out) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -27,28 +27,23 @@
 // types, the row's scan and message, a sample's load, the decisions) and a
 // route (TableRoute<staged / L2>, CirculantRoute: the tables, which rows a
 // thread runs in a layer and where their columns and messages are, the
-// syndrome).
+// syndrome).  What surrounds them -- a sample's Lci, the workgroup's
+// reduction words, a frame's outputs, the frame queue -- is in
+// ldpc_wgframe.hpp, shared with the on-chip flooding kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <limits>
 
+#include "ldpc_dispatch.hpp"
 #include "ldpc_layered.hpp"
 #include "ldpc_qc.hpp"
+#include "ldpc_wgframe.hpp"
 
 namespace ldpc {
 namespace {
 
 // ---- the arithmetics -------------------------------------------------------------
-
-// tx = in * polarity, then Lci = -tx (:149-153, :318-321) as an operation of
-// its own: folded into one multiply by -polarity, a NaN sample would keep the
-// sign that negating tx flips.
-__device__ __forceinline__ float ly_lci(float in, float polarity) {
-  float tx = in * polarity;
-  asm volatile("" : "+v"(tx));
-  return -tx;
-}
 
 // The float contract (include/ldpc_hip.h), Real = double or
 // float, a = scale:
@@ -224,28 +219,10 @@ __device__ __forceinline__ void row_loop(const Arith &ar, const Addr &ad, int d,
   }
 }
 
-// The per-wave syndrome counts summed over the workgroup: every thread gets
-// the sum.  One barrier; the layers' barriers separate this call's reads of
-// red[] from the next call's writes.
-__device__ __forceinline__ int ly_sum_waves(int cnt, int *red) {
-  const int tid = threadIdx.x, T = blockDim.x;
-  if ((tid & 63) == 0) red[tid >> 6] = cnt;
-  __syncthreads();
-  int w = 0;
-  const int nwaves = T >> 6;
-  for (int i = 0; i < nwaves; ++i) w += red[i];
-  return w;
-}
-
 // ---- the table route -------------------------------------------------------------
 
 constexpr int kRegsShort = 8, kRegsLong = 16;
 static_assert(kRegsLong <= kQcEntPad, "a register row is loaded whole from any entry");
-
-template <typename T>
-__device__ __forceinline__ void ly_copy(T *dst, const T *src, int n) {
-  for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
-}
 
 // A row of the per-edge tables: ci its first column index, its messages at Rr[k].
 struct TabAddr {
@@ -281,10 +258,10 @@ struct TableRoute {
       uint16_t *s_ci = reinterpret_cast<uint16_t *>(smem + lay.ci);
       uint16_t *s_order = reinterpret_cast<uint16_t *>(smem + lay.order);
       uint32_t *s_off = reinterpret_cast<uint32_t *>(smem + lay.off);
-      ly_copy(s_rows, gv.rows, M);
-      ly_copy(s_ci, gv.ci, gv.E);
-      ly_copy(s_order, gv.order, M);
-      ly_copy(s_off, gv.off, L + 1);
+      wg_copy(s_rows, gv.rows, M);
+      wg_copy(s_ci, gv.ci, gv.E);
+      wg_copy(s_order, gv.order, M);
+      wg_copy(s_off, gv.off, L + 1);
       rows = s_rows;
       ci = s_ci;
       order = s_order;
@@ -340,7 +317,7 @@ struct TableRoute {
       }
       cnt += __popcll(__ballot(Arith::odd(x)));
     }
-    return ly_sum_waves(cnt, red);
+    return wg_sum_waves(cnt, red);
   }
 };
 
@@ -483,7 +460,7 @@ struct CirculantRoute {
 #pragma unroll
       for (int s = 0; s < kSynRows; ++s) cnt += __popcll(__ballot(Arith::odd(x[s]) & mine));
     }
-    return ly_sum_waves(cnt, red);
+    return wg_sum_waves(cnt, red);
   }
 };
 
@@ -492,7 +469,8 @@ struct CirculantRoute {
 // Frame b into LDS: LQ = the samples' Lci in the arithmetic's format, R = 0;
 // ends with the barrier that lets the first layer read them.  The layered
 // entry points take strided frames only (no window lists, no second-polarity
-// half: DecodeArgs::win and pm_half are unset).
+// half: DecodeArgs::win and pm_half are unset), so this is frame_src's last
+// line alone; the general case is frame_src (ldpc_wgframe.hpp).
 template <typename Arith>
 __device__ __forceinline__ void load_frame(const Arith &ar, const DecodeArgs &a, int64_t b, int N,
                                            int E, const LayeredLayout &lay,
@@ -500,14 +478,13 @@ __device__ __forceinline__ void load_frame(const Arith &ar, const DecodeArgs &a,
   const int tid = threadIdx.x, T = blockDim.x;
   const float pol = a.polarity;
   const float *src = a.in + b * a.cw_stride;
-  for (int i = tid; i < N; i += T) LQ[i] = ar.sample(ly_lci(src[(int64_t)i * a.elem_stride], pol));
+  for (int i = tid; i < N; i += T) LQ[i] = ar.sample(lci_of(src[(int64_t)i * a.elem_stride], pol));
   Arith::clear(R, E, lay);
   __syncthreads();
 }
 
 // Frame b's outputs (the syndrome's barrier is behind every LQ write): the
-// decisions, the iterations used and the syndrome weight, the float
-// posteriors, and the info bits M.., MSB first (:207-219).
+// decisions into hard[N] where the arithmetic keeps them, then wg_store_frame.
 template <typename Arith>
 __device__ __forceinline__ void store_frame(const DecodeArgs &a, int64_t b, int M, int N, int KB,
                                             int used, int weight, const typename Arith::Post *LQ,
@@ -523,34 +500,7 @@ __device__ __forceinline__ void store_frame(const DecodeArgs &a, int64_t b, int 
     else
       return Arith::decision(LQ[i]);
   };
-  if (tid == 0) {
-    if (a.iters) a.iters[b] = used;
-    if (a.synd) a.synd[b] = weight;
-  }
-  if (a.bits)
-    for (int i = tid; i < N; i += T) a.bits[b * N + i] = bit(i);
-  if (a.llr)
-    for (int i = tid; i < N; i += T) a.llr[b * N + i] = (float)LQ[i];
-  for (int p = tid; p < KB; p += T) {
-    uint32_t o = 0;
-    for (int j = 0; j < 8; ++j) {
-      const int c = M + 8 * p + j;
-      if (c < N) o |= bit(c) << (7 - j);
-    }
-    a.packed[b * KB + p] = (uint8_t)o;
-  }
-}
-
-// The workgroup's next frame (the barrier also ends this frame's LDS reads):
-// a fixed stride, or the stream's counter.
-__device__ __forceinline__ int64_t ly_next_frame(const DecodeArgs &a, int64_t b, int *red) {
-  if (a.static_stride) {
-    __syncthreads();
-    return b + a.waves;
-  }
-  if (threadIdx.x == 0) red[16] = (int)(atomicAdd(a.ticket, 1u) - a.ticket_base);
-  __syncthreads();
-  return (int64_t)a.waves + (int64_t)red[16];
+  wg_store_frame(a, b, M, N, KB, used, weight, bit, [&](int i) { return (float)LQ[i]; });
 }
 
 template <typename Arith, typename Route>
@@ -586,38 +536,18 @@ __global__ void __launch_bounds__(kLayeredMaxThreads)
       }
     }
     store_frame<Arith>(a, b, gv.M, gv.N, gv.KB, used, weight, LQ, hard);
-    b = ly_next_frame(a, b, red);
+    b = wg_next_frame(a, b, red);
   }
 }
 
 // ---- the launch ------------------------------------------------------------------
 
-// The workgroups the device holds of kernel `fn` at `threads` threads and
-// `bytes` of dynamic LDS (looked up once per kernel and layout: resident ==
-// 0).  The LDS attribute belongs to the kernel, not to the caller: it allows
-// any layout layered_layout accepts.  False on a runtime error.
-bool ly_resident(const void *fn, int threads, int bytes, int &resident) {
-  if (resident != 0) return true;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLayeredLdsLimit) !=
-      hipSuccess)
-    return false;
-  int per_cu = 0, dev = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, (size_t)bytes) !=
-          hipSuccess ||
-      per_cu < 1 || hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      cus < 1)
-    return false;
-  resident = per_cu * cus;
-  return true;
-}
-
 template <typename Arith, typename Route>
 int launch_kernel(const typename Route::View &g, DecodeArgs a, const LayeredLayout &lay, Arith ar,
-                  hipStream_t st, int &resident) {
-  const void *fn = (const void *)layered_kernel<Arith, Route>;
-  if (!ly_resident(fn, lay.threads, lay.total, resident)) return -3;
-  a.waves = (int)std::min<int64_t>(a.B, resident);
+                  hipStream_t st, int &resident, uint32_t *advance_out) {
+  if (!wg_launch((const void *)layered_kernel<Arith, Route>, lay.threads, lay.total, resident, a,
+                 advance_out))
+    return -3;
   hipLaunchKernelGGL((layered_kernel<Arith, Route>), dim3((unsigned)a.waves),
                      dim3((unsigned)lay.threads), (size_t)lay.total, st, g, a, lay, ar);
   return hipGetLastError() == hipSuccess ? 0 : -3;
@@ -629,16 +559,14 @@ int launch_route(const typename Route::View &g, const DecodeArgs &args, const La
   *advance_out = 0;
   if (args.B <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  int rc;
   if (ar.kind == kLayeredQ8)
-    rc = launch_kernel<Q8Arith, Route>(g, args, lay, {ar.num, ar.llr_scale}, st, *resident);
-  else if (ar.kind == kLayeredF32)
-    rc = launch_kernel<FloatArith<float>, Route>(g, args, lay, {(float)ar.scale}, st, *resident);
-  else
-    rc = launch_kernel<FloatArith<double>, Route>(g, args, lay, {ar.scale}, st, *resident);
-  // one add per frame decoded, each workgroup's last being the one past the batch
-  if (rc == 0 && !args.static_stride) *advance_out = (uint32_t)args.B;
-  return rc;
+    return launch_kernel<Q8Arith, Route>(g, args, lay, {ar.num, ar.llr_scale}, st, *resident,
+                                         advance_out);
+  if (ar.kind == kLayeredF32)
+    return launch_kernel<FloatArith<float>, Route>(g, args, lay, {(float)ar.scale}, st, *resident,
+                                                   advance_out);
+  return launch_kernel<FloatArith<double>, Route>(g, args, lay, {ar.scale}, st, *resident,
+                                                  advance_out);
 }
 
 }  // namespace

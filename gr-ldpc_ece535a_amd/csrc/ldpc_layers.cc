@@ -7,13 +7,6 @@
 #include <algorithm>
 
 namespace ldpc {
-namespace {
-
-constexpr int kRedBytes = 128;
-
-constexpr int64_t al16(int64_t x) { return (x + 15) & ~(int64_t)15; }
-
-}  // namespace
 
 int plan_layers(int M, int N, const int32_t *rp, const int32_t *ci,
                 std::vector<int32_t> &layer_of_row) {
@@ -73,57 +66,53 @@ int check_layers(int M, int N, const int32_t *rp, const int32_t *ci, const int32
   return L;
 }
 
+namespace {
+
+// What the two layouts share behind the frame's own regions: the reduction
+// words, the tables where there is room for all of them (`stage`: the route
+// has tables to stage), the totals and the workgroup's size.
+void finish_layout(LdsCarve &c, int M, int64_t E, int L, int max_layer_rows, bool fits, bool stage,
+                   LayeredLayout &lay) {
+  lay.red = c.take(kWgRedBytes);
+  const int64_t frame = c.end;
+  lay.rows = c.take((int64_t)M * 4);
+  lay.ci = c.take(E * 2);
+  lay.order = c.take((int64_t)M * 2);
+  lay.off = c.take(((int64_t)L + 1) * 4);
+  const bool staged = stage && fits && c.end <= kLayeredLdsLimit;
+  lay.staged = staged ? 1 : 0;
+  lay.frame = LdsCarve::sat(frame);
+  lay.total = LdsCarve::sat(staged ? c.end : frame);
+  lay.threads = (int)std::min<int64_t>(
+      kLayeredMaxThreads, std::max<int64_t>(64, ((int64_t)max_layer_rows + 63) / 64 * 64));
+}
+
+}  // namespace
+
 bool layered_layout(int M, int N, int E, int dc_max, int L, int max_layer_rows, int prec,
                     LayeredLayout &lay) {
   const int64_t real = prec == 1 ? 4 : 8;
-  const int64_t r = al16((int64_t)N * real), hard = r + al16((int64_t)E * real);
-  const int64_t red = hard + al16(N), frame = red + kRedBytes;
-  const int64_t threads = std::min<int64_t>(
-      kLayeredMaxThreads, std::max<int64_t>(64, ((int64_t)max_layer_rows + 63) / 64 * 64));
-  const bool fits = frame <= kLayeredLdsLimit && M <= kLayeredIndexMax && N <= kLayeredIndexMax &&
-                    E <= kLayeredIndexMax && dc_max <= kLayeredDcMax;
-  // the tables behind the frame, where there is room for all of them
-  const int64_t rows = frame, ci = rows + al16((int64_t)M * 4), order = ci + al16((int64_t)E * 2);
-  const int64_t off = order + al16((int64_t)M * 2), staged_total = off + al16(((int64_t)L + 1) * 4);
-  const bool staged = fits && staged_total <= kLayeredLdsLimit;
-  const int64_t cap = 0x7fffffff;
-  lay.r = (int)std::min(r, cap);
-  lay.hard = (int)std::min(hard, cap);
-  lay.red = (int)std::min(red, cap);
-  lay.rows = (int)std::min(rows, cap);
-  lay.ci = (int)std::min(ci, cap);
-  lay.order = (int)std::min(order, cap);
-  lay.off = (int)std::min(off, cap);
-  lay.staged = staged ? 1 : 0;
-  lay.frame = (int)std::min(frame, cap);
-  lay.total = (int)std::min(staged ? staged_total : frame, cap);
-  lay.threads = (int)threads;
+  LdsCarve c;
+  c.take((int64_t)N * real);  // LQ
+  lay.r = c.take((int64_t)E * real);
+  lay.hard = c.take(N);
+  const bool fits = c.end + kWgRedBytes <= kLayeredLdsLimit && M <= kLayeredIndexMax &&
+                    N <= kLayeredIndexMax && E <= kLayeredIndexMax && dc_max <= kLayeredDcMax;
+  finish_layout(c, M, E, L, max_layer_rows, fits, true, lay);
   return fits;
 }
 
 bool layered_q8_layout(int M, int N, int64_t E, int dc_max, int dv_max, int L,
                        int max_layer_rows, int Z, LayeredLayout &lay) {
   const bool tables = Z <= 0;
-  const int64_t r = al16((int64_t)N * 2), red = r + al16(E), frame = red + kRedBytes;
-  const int64_t threads = std::min<int64_t>(
-      kLayeredMaxThreads, std::max<int64_t>(64, ((int64_t)max_layer_rows + 63) / 64 * 64));
-  const bool fits = frame <= kLayeredLdsLimit && M <= kLayeredIndexMax && N <= kLayeredIndexMax &&
-                    (tables ? E : E / Z) <= kLayeredIndexMax && dc_max <= kLayeredDcMax &&
-                    dv_max <= kLayeredQ8DvMax;
-  const int64_t rows = frame, ci = rows + al16((int64_t)M * 4), order = ci + al16(E * 2);
-  const int64_t off = order + al16((int64_t)M * 2), staged_total = off + al16(((int64_t)L + 1) * 4);
-  const bool staged = tables && fits && staged_total <= kLayeredLdsLimit;
-  const int64_t cap = 0x7fffffff;
-  lay.r = (int)std::min(r, cap);
-  lay.hard = lay.red = (int)std::min(red, cap);
-  lay.rows = (int)std::min(rows, cap);
-  lay.ci = (int)std::min(ci, cap);
-  lay.order = (int)std::min(order, cap);
-  lay.off = (int)std::min(off, cap);
-  lay.staged = staged ? 1 : 0;
-  lay.frame = (int)std::min(frame, cap);
-  lay.total = (int)std::min(staged ? staged_total : frame, cap);
-  lay.threads = (int)threads;
+  LdsCarve c;
+  c.take((int64_t)N * 2);  // LQ
+  lay.r = c.take(E);
+  lay.hard = LdsCarve::sat(c.end);  // unused: the decisions are read in place
+  const bool fits = c.end + kWgRedBytes <= kLayeredLdsLimit && M <= kLayeredIndexMax &&
+                    N <= kLayeredIndexMax && (tables ? E : E / Z) <= kLayeredIndexMax &&
+                    dc_max <= kLayeredDcMax && dv_max <= kLayeredQ8DvMax;
+  finish_layout(c, M, E, L, max_layer_rows, fits, tables, lay);
   return fits;
 }
 

@@ -13,11 +13,13 @@
 #include <string>
 #include <vector>
 
+#include "ldpc_wglimits.hpp"
+
 namespace ldpc {
 
-constexpr int kLayeredLdsLimit = 160 * 1024;  // LDS a workgroup may declare on MI355X
-constexpr int kLayeredMaxThreads = 1024;
-constexpr int kLayeredIndexMax = 65535;       // M, N, E: the tables' 16-bit fields
+constexpr int kLayeredLdsLimit = kWgLdsLimit;
+constexpr int kLayeredMaxThreads = kWgMaxThreads;
+constexpr int kLayeredIndexMax = kWgIndexMax;
 constexpr int kLayeredDcMax = 32;
 
 // First fit over the rows in ascending order: row j goes to the lowest layer
@@ -36,7 +38,7 @@ int check_layers(int M, int N, const int32_t *rp, const int32_t *ci, const int32
 //   LQ    Real[N]  posteriors L(Q_i), at offset 0
 //   R     Real[E]  check -> bit messages
 //   hard  uint8[N] hard decisions
-//   red   per-wave syndrome counts, the next frame's index
+//   red   the workgroup's reduction words (ldpc_wglimits.hpp)
 // and, where they fit behind the frame (`staged`), copies of the code's
 // tables (LayeredTables); otherwise the kernel reads them from global memory
 // (L2).  E + N reals per frame, where the flooding on-chip path needs 2 E.

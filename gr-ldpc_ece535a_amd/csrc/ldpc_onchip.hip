@@ -7,10 +7,11 @@
 // grid-wide launches per iteration.  A code of a few thousand edges fits the
 // 160 KiB of LDS a workgroup may declare, so here a persistent workgroup
 // decodes one frame at a time entirely on chip and then takes the next frame
-// from the launch's queue (DecodeArgs::ticket).  Threads stride over the
-// edges (check pass, bit messages), the columns (posterior, hard decision) and
-// the rows (syndrome); the passes are separated by workgroup barriers and no
-// workgroup ever waits on another.
+// (ldpc_wgframe.hpp: the frame's source, the wave sum and the queue, shared
+// with the layered kernels).  Threads stride over the edges (check pass, bit
+// messages), the columns (posterior, hard decision) and the rows (syndrome);
+// the passes are separated by workgroup barriers and no workgroup ever waits
+// on another.
 //
 // The per-edge arithmetic is the reference's, in its order (min-sum
 // lib/ldpc_decoder_cb_impl.cc:350-403, sum-product :503-553), with the same
@@ -20,33 +21,16 @@
 #include <algorithm>
 
 #include "ldpc_device.hpp"
+#include "ldpc_dispatch.hpp"
 #include "ldpc_onchip.hpp"
+#include "ldpc_wgframe.hpp"
 
 namespace ldpc {
 namespace {
 
-constexpr int kRedWords = 32;  // [0, 16): per-wave counts, [16]: next frame
-
-constexpr int64_t al16(int64_t x) { return (x + 15) & ~(int64_t)15; }
-
 template <int PREC>
 constexpr int tab_bytes() {
   return Math<PREC>::kTabN > 0 ? (int)sizeof(typename Math<PREC>::Tab) * Math<PREC>::kTabN : 0;
-}
-
-// Frame b's samples and polarity (DecodeArgs: win, pm_half).
-__device__ __forceinline__ const float *oc_frame_src(const DecodeArgs &a, int64_t b, float &pol) {
-  if (a.win) {
-    const int64_t w = a.win[b];
-    pol = (w & 1) ? -a.polarity : a.polarity;
-    return a.in + (w >> 1) * a.elem_stride;
-  }
-  pol = a.polarity;
-  if (a.pm_half > 0 && b >= a.pm_half) {
-    b -= a.pm_half;
-    pol = -pol;
-  }
-  return a.in + b * a.cw_stride;
 }
 
 // The code's tables as the kernel reads them: LDS copies or global memory.
@@ -60,14 +44,8 @@ struct OcTabs {
   int M, N, E;
 };
 
-template <typename T>
-__device__ __forceinline__ void oc_copy(T *dst, const T *src, int n) {
-  for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
-}
-
 // Syndrome weight of the hard decisions in LDS (checkFrame :236-253, no
-// threshold): every thread gets the sum.  One barrier; the caller's next
-// barrier separates this call's reads of red[] from the next call's writes.
+// threshold): every thread gets the sum (wg_sum_waves: one barrier).
 __device__ __forceinline__ int oc_syndrome(const OcTabs &g, const uint8_t *hard, int *red) {
   const int tid = threadIdx.x, T = blockDim.x;
   int cnt = 0;
@@ -83,12 +61,7 @@ __device__ __forceinline__ int oc_syndrome(const OcTabs &g, const uint8_t *hard,
     }
     cnt += __popcll(__ballot(odd));
   }
-  if ((tid & 63) == 0) red[tid >> 6] = cnt;
-  __syncthreads();
-  int w = 0;
-  const int nwaves = T >> 6;
-  for (int i = 0; i < nwaves; ++i) w += red[i];
-  return w;
+  return wg_sum_waves(cnt, red);
 }
 
 // Column i's posterior from the check messages in R: the ascending-row sum
@@ -136,12 +109,12 @@ __global__ void __launch_bounds__(kOnchipMaxThreads)
     uint32_t *cols = reinterpret_cast<uint32_t *>(smem + L.cols);
     uint16_t *ci = reinterpret_cast<uint16_t *>(smem + L.ci);
     uint16_t *ce = reinterpret_cast<uint16_t *>(smem + L.ce);
-    oc_copy(erow, gv.erow, E);
-    oc_copy(ecol, gv.ecol, E);
-    oc_copy(rows, gv.rows, M);
-    oc_copy(cols, gv.cols, N);
-    oc_copy(ci, gv.ci, E);
-    oc_copy(ce, gv.ce, E);
+    wg_copy(erow, gv.erow, E);
+    wg_copy(ecol, gv.ecol, E);
+    wg_copy(rows, gv.rows, M);
+    wg_copy(cols, gv.cols, N);
+    wg_copy(ci, gv.ci, E);
+    wg_copy(ce, gv.ce, E);
     g.erow = erow;
     g.ecol = ecol;
     g.rows = rows;
@@ -161,16 +134,9 @@ __global__ void __launch_bounds__(kOnchipMaxThreads)
   int64_t b = blockIdx.x;
   while (b < a.B) {
     float pol;
-    const float *src = oc_frame_src(a, b, pol);
+    const float *src = frame_src(a, b, pol);
     // channel samples: tx = in * polarity (:149-153), kept as -tx (Lci :318-321, r :486)
-    for (int i = tid; i < N; i += T) {
-      float tx = src[(int64_t)i * a.elem_stride] * pol;
-      // two operations, as in the reference: folded into one multiply by
-      // -polarity, a NaN sample would keep the sign that negating tx flips,
-      // and the posteriors it reaches would differ in their sign bit
-      asm volatile("" : "+v"(tx));
-      chan[i] = -tx;
-    }
+    for (int i = tid; i < N; i += T) chan[i] = lci_of(src[(int64_t)i * a.elem_stride], pol);
     __syncthreads();
     // first bit -> check messages (:328-331, :489-496)
     for (int e = tid; e < E; e += T) {
@@ -240,6 +206,14 @@ __global__ void __launch_bounds__(kOnchipMaxThreads)
       __syncthreads();
     }
     // outputs: R and hard are those of the frame's last iteration
+    // A copy of wg_store_frame (ldpc_wgframe.hpp) with bit(i) = hard[i] and
+    // llr(i) = oc_posterior: through the helper all 12 kernels kept their
+    // registers and changed in code length (-800 to +256 bytes), and the
+    // sum-product kernel with its tables in L2 measured 1.4 to 1.7 % slower on
+    // every N = 2160 leg (profiles/round19/wgframe_ab.txt, series 1; the
+    // lengths: wgframe_isa.txt).  Only that kernel failed; the body stays for
+    // all 12 all the same: one copy is less code than the helper and the copy
+    // side by side under an `if constexpr`.
     if (tid == 0) {
       if (a.iters) a.iters[b] = used;
       if (a.synd) a.synd[b] = weight;
@@ -256,15 +230,7 @@ __global__ void __launch_bounds__(kOnchipMaxThreads)
       }
       a.packed[b * gv.KB + p] = (uint8_t)o;
     }
-    // next frame (the barrier also ends this frame's LDS reads)
-    if (a.static_stride) {
-      __syncthreads();
-      b += a.waves;
-    } else {
-      if (tid == 0) red[16] = (int)(atomicAdd(a.ticket, 1u) - a.ticket_base);
-      __syncthreads();
-      b = (int64_t)a.waves + (int64_t)red[16];
-    }
+    b = wg_next_frame(a, b, red);
   }
 }
 
@@ -275,24 +241,10 @@ int tab_bytes_of(int method, int prec) {
 
 template <int PREC, int METHOD, bool STAGED>
 int launch_kernel(const OnchipView &g, DecodeArgs a, const OnchipLayout &L, hipStream_t st,
-                  int &resident) {
-  const void *fn = (const void *)onchip_decode_kernel<PREC, METHOD, STAGED>;
-  if (resident == 0) {
-    // the attribute belongs to the kernel, not to this code: allow any layout
-    // onchip_plan accepts
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kOnchipLdsLimit) !=
-        hipSuccess)
-      return -3;
-    int per_cu = 0, dev = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, L.threads, (size_t)L.total) !=
-            hipSuccess ||
-        per_cu < 1 || hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus < 1)
-      return -3;
-    resident = per_cu * cus;
-  }
-  a.waves = (int)std::min<int64_t>(a.B, resident);
+                  int &resident, uint32_t *advance_out) {
+  if (!wg_launch((const void *)onchip_decode_kernel<PREC, METHOD, STAGED>, L.threads, L.total,
+                 resident, a, advance_out))
+    return -3;
   hipLaunchKernelGGL((onchip_decode_kernel<PREC, METHOD, STAGED>), dim3((unsigned)a.waves),
                      dim3((unsigned)L.threads), (size_t)L.total, st, g, a, L);
   return hipGetLastError() == hipSuccess ? 0 : -3;
@@ -300,9 +252,9 @@ int launch_kernel(const OnchipView &g, DecodeArgs a, const OnchipLayout &L, hipS
 
 template <int PREC, int METHOD>
 int launch_one(const OnchipView &g, const DecodeArgs &a, const OnchipLayout &L, hipStream_t st,
-               int &resident) {
-  return L.staged ? launch_kernel<PREC, METHOD, true>(g, a, L, st, resident)
-                  : launch_kernel<PREC, METHOD, false>(g, a, L, st, resident);
+               int &resident, uint32_t *advance_out) {
+  return L.staged ? launch_kernel<PREC, METHOD, true>(g, a, L, st, resident, advance_out)
+                  : launch_kernel<PREC, METHOD, false>(g, a, L, st, resident, advance_out);
 }
 
 }  // namespace
@@ -310,35 +262,29 @@ int launch_one(const OnchipView &g, const DecodeArgs &a, const OnchipLayout &L, 
 bool onchip_plan(int M, int N, int E, int dc_max, int dv_max, int method, int prec,
                  OnchipLayout &L) {
   const int64_t real = prec == 1 ? 4 : 8;
-  const int64_t msgs = al16((int64_t)E * real);
-  const int64_t tab = 2 * msgs, chan = tab + al16(tab_bytes_of(method, prec));
-  const int64_t hard = chan + al16((int64_t)N * 4), red = hard + al16(N);
-  const int64_t frame = red + kRedWords * 4;
-  const int64_t threads =
-      std::min<int64_t>(kOnchipMaxThreads, std::max<int64_t>(64, ((int64_t)E + 63) / 64 * 64));
+  LdsCarve c;
+  c.take((int64_t)E * real);  // A
+  L.r = c.take((int64_t)E * real);
+  L.tab = c.take(tab_bytes_of(method, prec));
+  L.chan = c.take((int64_t)N * 4);
+  L.hard = c.take(N);
+  L.red = c.take(kWgRedBytes);
+  const int64_t frame = c.end;
   const bool fits = frame <= kOnchipLdsLimit && M <= kOnchipIndexMax && N <= kOnchipIndexMax &&
                     E <= kOnchipIndexMax && dc_max <= kGraphDcMax && dv_max <= kGraphDvMax;
   // the tables behind the frame, where there is room for all of them
-  const int64_t erow = frame, ecol = erow + al16((int64_t)E * 4), rows = ecol + al16((int64_t)E * 8);
-  const int64_t cols = rows + al16((int64_t)M * 4), ci = cols + al16((int64_t)N * 4);
-  const int64_t ce = ci + al16((int64_t)E * 2), staged_total = ce + al16((int64_t)E * 2);
-  const bool staged = fits && staged_total <= kOnchipLdsLimit;
-  const int64_t cap = 0x7fffffff;
-  L.r = (int)std::min(msgs, cap);
-  L.tab = (int)std::min(tab, cap);
-  L.chan = (int)std::min(chan, cap);
-  L.hard = (int)std::min(hard, cap);
-  L.red = (int)std::min(red, cap);
-  L.erow = (int)std::min(erow, cap);
-  L.ecol = (int)std::min(ecol, cap);
-  L.rows = (int)std::min(rows, cap);
-  L.cols = (int)std::min(cols, cap);
-  L.ci = (int)std::min(ci, cap);
-  L.ce = (int)std::min(ce, cap);
+  L.erow = c.take((int64_t)E * 4);
+  L.ecol = c.take((int64_t)E * 8);
+  L.rows = c.take((int64_t)M * 4);
+  L.cols = c.take((int64_t)N * 4);
+  L.ci = c.take((int64_t)E * 2);
+  L.ce = c.take((int64_t)E * 2);
+  const bool staged = fits && c.end <= kOnchipLdsLimit;
   L.staged = staged ? 1 : 0;
-  L.frame = (int)std::min(frame, cap);
-  L.total = (int)std::min(staged ? staged_total : frame, cap);
-  L.threads = (int)threads;
+  L.frame = LdsCarve::sat(frame);
+  L.total = LdsCarve::sat(staged ? c.end : frame);
+  L.threads = (int)std::min<int64_t>(kOnchipMaxThreads,
+                                     std::max<int64_t>(64, ((int64_t)E + 63) / 64 * 64));
   return fits;
 }
 
@@ -379,21 +325,17 @@ int launch_onchip_decode(const OnchipView &g, const DecodeArgs &args, int method
   OnchipLayout L;
   if (!onchip_plan(g.M, g.N, g.E, g.dc_max, g.dv_max, method, prec, L)) return -2;
   hipStream_t st = (hipStream_t)stream;
-  int rc;
   if (method == 1) {
     int &res = resident[1][prec];
-    rc = prec == 1   ? launch_one<1, 1>(g, args, L, st, res)
-         : prec == 2 ? launch_one<2, 1>(g, args, L, st, res)
-         : prec == 3 ? launch_one<3, 1>(g, args, L, st, res)
-                     : launch_one<0, 1>(g, args, L, st, res);
-  } else {
-    // min-sum has no transcendentals: the f64 modes are one kernel
-    int &res = resident[0][prec == 1 ? 1 : 0];
-    rc = prec == 1 ? launch_one<1, 0>(g, args, L, st, res) : launch_one<0, 0>(g, args, L, st, res);
+    return prec == 1   ? launch_one<1, 1>(g, args, L, st, res, advance_out)
+           : prec == 2 ? launch_one<2, 1>(g, args, L, st, res, advance_out)
+           : prec == 3 ? launch_one<3, 1>(g, args, L, st, res, advance_out)
+                       : launch_one<0, 1>(g, args, L, st, res, advance_out);
   }
-  // one add per frame decoded, each workgroup's last being the one past the batch
-  if (rc == 0 && !args.static_stride) *advance_out = (uint32_t)args.B;
-  return rc;
+  // min-sum has no transcendentals: the f64 modes are one kernel
+  int &res = resident[0][prec == 1 ? 1 : 0];
+  return prec == 1 ? launch_one<1, 0>(g, args, L, st, res, advance_out)
+                   : launch_one<0, 0>(g, args, L, st, res, advance_out);
 }
 
 }  // namespace ldpc

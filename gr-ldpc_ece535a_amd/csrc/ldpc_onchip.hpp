@@ -17,12 +17,13 @@
 
 #include "ldpc_graph.hpp"
 #include "ldpc_kernels.hpp"
+#include "ldpc_wglimits.hpp"
 
 namespace ldpc {
 
-constexpr int kOnchipLdsLimit = 160 * 1024;  // LDS a workgroup may declare on MI355X
-constexpr int kOnchipMaxThreads = 1024;
-constexpr int kOnchipIndexMax = 65535;       // M, N, E: the tables' 16-bit fields
+constexpr int kOnchipLdsLimit = kWgLdsLimit;
+constexpr int kOnchipMaxThreads = kWgMaxThreads;
+constexpr int kOnchipIndexMax = kWgIndexMax;
 
 // Byte offsets of one frame's state in the workgroup's dynamic LDS.
 //   A     Real[E]  bit -> check: tanh(M/2) (sum-product) or L(q) (min-sum)
@@ -30,7 +31,7 @@ constexpr int kOnchipIndexMax = 65535;       // M, N, E: the tables' 16-bit fiel
 //   tab   the mode's log table (sum-product; stage_tab)
 //   chan  float[N] -tx (widening to Real is exact)
 //   hard  uint8[N] hard decisions
-//   red   per-wave syndrome counts, the next frame's index
+//   red   the workgroup's reduction words (ldpc_wglimits.hpp)
 // and, where they fit behind the frame (`staged`), copies of the code's
 // tables (OnchipTables), made once per workgroup; otherwise the kernels read
 // the tables from global memory (L2) in every pass.
