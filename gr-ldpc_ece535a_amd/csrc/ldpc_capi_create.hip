@@ -170,6 +170,20 @@ int build_tables(ldpc_ctx *ctx, std::vector<EdgeRowRec> &erecs, std::vector<Edge
   for (int j = 0; j < M; ++j)
     for (int i = 0; i < N; ++i)
       if (H[(size_t)j * N + i]) rowmask[(size_t)j * nw + pos[i] / 64] |= 1ull << (pos[i] % 64);
+  // behind the row masks, the static zero lanes of the column-centric
+  // sum-product (CodeView::rowmask): word q * kDvMax + k has bit l set when
+  // entry k of position l + 64 q is the only entry its column can have --
+  // every other entry of the record is missing (a column of degree 1 gives
+  // its entry 0, a column of degree 0 or a position past N all of them).
+  // That entry's bit message, the sum over the column's other entries, is then
+  // the empty sum +0.0 in every iteration of every all-finite frame.
+  rowmask.resize((size_t)M * nw + (size_t)nw * ldpc::kDvMax, 0);
+  for (int p = 0; p < 64 * nw; ++p)
+    for (int k = 0; k < ldpc::kDvMax; ++k) {
+      bool alone = true;
+      for (int k2 = 0; k2 < ldpc::kDvMax; ++k2) alone = alone && (k2 == k || cols[p].e[k2] == kNone);
+      if (alone) rowmask[(size_t)M * nw + (size_t)(p / 64) * ldpc::kDvMax + k] |= 1ull << (p % 64);
+    }
   return LDPC_OK;
 }
 

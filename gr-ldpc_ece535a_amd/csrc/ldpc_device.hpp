@@ -51,6 +51,13 @@ struct Math<0> {
                                                      const Tab *tab) {
     ex::tanh_half_n<n>(m, z, tab);
   }
+  // the column-centric loop's form: zero[i] = the lanes where m[i] is a
+  // structural zero (ex::tanh_half_n's masked overload)
+  template <int n>
+  static __device__ __forceinline__ void tanh_half_n(const double (&m)[n], double (&z)[n],
+                                                     const Tab *tab, const uint64_t (&zero)[n]) {
+    ex::tanh_half_n<n>(m, z, tab, zero);
+  }
   template <int n>
   static __device__ __forceinline__ void check_msg_n(const double (&T)[n], const Tab *tab,
                                                      double (&E)[n]) {
@@ -156,7 +163,9 @@ struct Math<1> {
 // back by their lanes.  Same functions, same results as ex::log_ratio_n.
 // A wave's LDS accesses execute in issue order, so only the compiler must be
 // kept from reordering them (the empty asm with a memory clobber).
-template <int n>
+// LEAN (the column-centric loop): the dense pass calls ex::log_near1_lean, the
+// same function without its register copies.
+template <int n, bool LEAN = false>
 __device__ __forceinline__ void log_ratio_n_packed(const double (&T)[n],
                                                    const ex::ExTab *tab, double (&E)[n],
                                                    double *scratch, int lane, uint32_t zero_at) {
@@ -194,9 +203,23 @@ __device__ __forceinline__ void log_ratio_n_packed(const double (&T)[n],
     for (int i = 0; i < n; ++i)
       if (packed[i]) scratch[pos[i]] = q[i];
     asm volatile("" ::: "memory");
-    for (uint32_t p = 0; p < base; p += 64) {
-      const uint32_t idx = p + (uint32_t)lane;
-      if (idx < base) scratch[idx] = ex::log_near1(scratch[idx]);
+    if constexpr (LEAN) {
+      // the first 64 packed ratios at the lane's own cell (no loop counter, no
+      // running address); a second or third pass only when there are more
+      // (9 % of wave-iterations on the headline workload, tools/path_stats.py)
+      if ((uint32_t)lane < base) scratch[lane] = ex::log_near1_lean(scratch[lane]);
+      if (base > 64) {
+        LDPC_EX_COLD();
+        for (uint32_t p = 64; p < base; p += 64) {
+          const uint32_t idx = p + (uint32_t)lane;
+          if (idx < base) scratch[idx] = ex::log_near1_lean(scratch[idx]);
+        }
+      }
+    } else {
+      for (uint32_t p = 0; p < base; p += 64) {
+        const uint32_t idx = p + (uint32_t)lane;
+        if (idx < base) scratch[idx] = ex::log_near1(scratch[idx]);
+      }
     }
     asm volatile("" ::: "memory");
   }

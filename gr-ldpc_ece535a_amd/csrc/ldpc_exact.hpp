@@ -90,6 +90,21 @@ LDPC_HD uint32_t hiw(double x) { return (uint32_t)(bits(x) >> 32); }
 LDPC_HD double from_hi(uint32_t h) { return dbl((uint64_t)h << 32); }
 LDPC_HD double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
 LDPC_HD double sel(bool c, double a, double b) { return c ? a : b; }
+// fma(s, a, c) with the wave-uniform constant s read from scalar registers and
+// the addend c read in place (the 3-address v_fma_f64).  For a constant or
+// still-live addend the compiler picks the 2-address v_fmac_f64 and copies c
+// into its destination first (one v_mov_b64 per call); this form needs no
+// copy.  One scalar source, gfx950's constant-bus limit.  The same fused
+// operation either way: the result is fma_(s, a, c) bit for bit.
+LDPC_HD double fma3_(double s, double a, double c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double d;
+  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "s"(s), "v"(a), "v"(c));
+  return d;
+#else
+  return __builtin_fma(s, a, c);
+#endif
+}
 
 #if !defined(__HIP_DEVICE_COMPILE__)
 // host tests only: perturbs the shared reciprocal by this many ulp, standing
@@ -266,7 +281,11 @@ constexpr ExTab make_ex_tab() {
 // test into its own rare-case test).  hx[i]: the high word of |u[i]|, or any
 // word that is above 0x3fd62e42 exactly when that one is.  k[i]: glibc's k
 // of u[i], handed back.
-template <int n>
+// LEAN (the column-centric loop's build): the byte offset k * 16 of the two
+// per-k tables' entries is formed once per value and kept for the second
+// lookup (the compiler otherwise shifts k again for the tail entry).  The
+// same entries, the same operations.
+template <int n, bool LEAN = false>
 LDPC_HD void expm1_n(const double (&u)[n], const uint32_t (&hx)[n], double (&t)[n], int (&k)[n],
                      const ExTab *tab, bool mid_possible = true) {
   constexpr double invln2 = 1.44269504088896338700e+00;
@@ -302,9 +321,22 @@ LDPC_HD void expm1_n(const double (&u)[n], const uint32_t (&hx)[n], double (&t)[
 #pragma unroll
     for (int i = 0; i < n; ++i) k[i] = hx[i] > 0x3fd62e42u ? k[i] : 0;
   }
+  static_assert(sizeof(RedEntry) == 16 && sizeof(TailEntry) == 16, "16-byte per-k entries");
+  int koff[n];  // LEAN: k * 16, the entries' byte offset from entry k = 0
 #pragma unroll
   for (int i = 0; i < n; ++i) {
-    const RedEntry re = tab->red[k[i] - kTailLo];
+    RedEntry re;
+    if constexpr (LEAN) {
+      koff[i] = k[i] * 16;
+#if defined(__HIP_DEVICE_COMPILE__)
+      asm("" : "+v"(koff[i]));  // one register for both lookups, not recomputed
+#endif
+      re = *reinterpret_cast<const RedEntry *>(reinterpret_cast<const char *>(tab->red - kTailLo) +
+                                               koff[i]);
+    } else {
+      koff[i] = 0;
+      re = tab->red[k[i] - kTailLo];
+    }
     const double hi = u[i] - re.khi;
     const double lo = re.klo;
     x[i] = hi - lo;
@@ -332,7 +364,12 @@ LDPC_HD void expm1_n(const double (&u)[n], const uint32_t (&hx)[n], double (&t)[
     // per-lane constants: A, B from the table (tail_entry).  fma(A - d, 2^k,
     // B) with its exact product is the exact scaling (ldexp, |k| <= 64 on
     // moderate values) followed by the one rounded addition
-    const TailEntry te = tab->tail[kk - kTailLo];
+    TailEntry te;
+    if constexpr (LEAN)
+      te = *reinterpret_cast<const TailEntry *>(reinterpret_cast<const char *>(tab->tail - kTailLo) +
+                                                koff[i]);
+    else
+      te = tab->tail[kk - kTailLo];
     t[i] = __builtin_ldexp(te.a - d, kk) + te.b;
   }
   if (mid_possible) {  // (a wave-uniform flag: the test stays in its branch)
@@ -373,10 +410,34 @@ LDPC_HD void expm1_n(const double (&u)[n], double (&t)[n], const ExTab *tab,
 // The n quotients share one reciprocal (div_n); lanes outside the expm1
 // range feed it a dummy argument and are selected away.
 // ---------------------------------------------------------------------------
-template <int n>
-LDPC_HD void tanh_half_n(const double (&m)[n], double (&z)[n], const ExTab *tab) {
+//
+// The masked form (MASKED, the overload with `zero`) is for a caller that
+// knows where its exact zeros are.  zero[i] holds the lanes (host: this
+// value's flag) whose m[i] is known to be +-0 whenever it is called: the
+// column-centric loop's empty leave-one-out sums, fixed per code
+// (build_tables' zero-lane masks).  `special` is then the range test AND-NOT
+// that mask: no m != 0.0 compare per value.  Why this computes the same z:
+//   * a masked lane holds +-0, which the range test flags and the mask
+//     removes -- exactly what the compare did: the general path returns m's
+//     own +-0 (above);
+//   * an exact zero at an UNMASKED lane (rare: sums of +-0.0 samples, or
+//     messages that cancel) is now in the special set.  The cold blocks then
+//     run: u is clamped to -2^-54 (k = 0, a finite t and q: no lane's shared
+//     reciprocal is disturbed -- the clamp leaves every in-range |m| as it
+//     is), and the last block replaces z by x (1 + x) with x = m / 2 = +-0,
+//     i.e. +-0 (1 +- 0) = +-0 with m's sign: glibc's return value for
+//     |x| < 2^-55, and the same +-0 the general path gave.  The other lanes of
+//     that wave take the any_special forms of u and of expm1's k = 20..56
+//     test, which equal the common forms on in-range operands (they are what
+//     every wave with a special lane has always run);
+//   * a mask bit set on a lane whose m is NOT zero would be wrong only if that
+//     m is outside [2^-54, 13.5): the mask must mark structural zeros only.
+// LEAN: expm1_n's one-shift table lookups (see there).
+template <int n, bool MASKED, bool LEAN>
+LDPC_HD void tanh_half_impl(const double (&m)[n], double (&z)[n], const ExTab *tab,
+                            const uint64_t *zero) {
   static_assert(n <= 8, "the tanh divisors (up to 2^63 each) share one prefix product");
-  double u[n], t[n], num[n], den[n], q[n];
+  double u[n], t[n], num[n], nneg[n], den[n], q[n];
   uint32_t hm[n];
   uint64_t special = 0;  // (device: lanes of the wave; host: this value's flag)
 #pragma unroll
@@ -395,8 +456,11 @@ LDPC_HD void tanh_half_n(const double (&m)[n], double (&z)[n], const ExTab *tab)
     // degree 1 has no other edge, so its bit message is the empty sum +0.0
     // every iteration (3 of the reference H's 64 columns), and with them in
     // the special set every wave took the special branches every iteration
-    special |= LDPC_EX_LANES(im - 0x3c900000u >= 0x402b0000u - 0x3c900000u) &
-               LDPC_EX_LANES(m[i] != 0.0);
+    if constexpr (MASKED)
+      special |= LDPC_EX_LANES(im - 0x3c900000u >= 0x402b0000u - 0x3c900000u) & ~zero[i];
+    else
+      special |= LDPC_EX_LANES(im - 0x3c900000u >= 0x402b0000u - 0x3c900000u) &
+                 LDPC_EX_LANES(m[i] != 0.0);
   }
   const bool any_special = special != 0;  // wave-uniform on the device
   uint64_t special_again = special;        // for the test after the divisions
@@ -425,11 +489,14 @@ LDPC_HD void tanh_half_n(const double (&m)[n], double (&z)[n], const ExTab *tab)
   // step; testing it saves the mask of hm's exponent bit.  (A NaN lane has
   // k = 0 whatever its bits: its z is replaced below.)
   int k[n];
-  expm1_n<n>(u, hx, t, k, tab, any_special);
+  expm1_n<n, LEAN>(u, hx, t, k, tab, any_special);
 #pragma unroll
   for (int i = 0; i < n; ++i) {
     const bool big = k[i] > 0;
-    num[i] = big ? 2.0 : -t[i];
+    // (the select is held negated, -2.0 or t, and its sign flipped where it is
+    // used: the form the compiler gives num anyway; LEAN reads its low word)
+    nneg[i] = big ? -2.0 : t[i];
+    num[i] = -nneg[i];
     den[i] = t[i] + 2.0;
   }
   div_n<n>(num, den, q);
@@ -441,7 +508,19 @@ LDPC_HD void tanh_half_n(const double (&m)[n], double (&z)[n], const ExTab *tab)
     // word is 0 either way) instead of a double one -- and the magnitude
     // goes in with the sign transfer
     const bool big = k[i] > 0;
-    const double r = q[i] + from_hi(big ? 0xbff00000u : 0u);
+    double w = from_hi(big ? 0xbff00000u : 0u);
+    if constexpr (LEAN) {
+      // w's low word taken from num[i] (read off nneg[i]: negation leaves the
+      // low word alone), dead by now, so that w is formed on
+      // num's high word with no zero to copy next to it.  Where |x| >= 1,
+      // num = 2.0 and w is -1.0 as above.  Elsewhere w is num's low word
+      // under a zero high word, a subnormal below 2^-1042, added to
+      // q = tanh|x| >= 2^-56 (or to q = +-0 at m = +-0, where num = -+0 and
+      // w = +0): far below half an ulp of q, so RN(q + w) = q = RN(q + 0).
+      // (Lanes outside the expm1 range are replaced below whatever r is.)
+      w = dbl(((uint64_t)(big ? 0xbff00000u : 0u) << 32) | (uint32_t)bits(nneg[i]));
+    }
+    const double r = q[i] + w;
     const uint32_t zh = (hiw(r) & 0x7fffffffu) | (hm[i] & 0x80000000u);
     z[i] = dbl(((uint64_t)zh << 32) | (uint32_t)bits(r));
   }
@@ -456,6 +535,18 @@ LDPC_HD void tanh_half_n(const double (&m)[n], double (&z)[n], const ExTab *tab)
       z[i] = ix < 0x3c800000u ? x * (1.0 + x) : (x != x ? x + x : z[i]);
     }
   }
+}
+
+template <int n>
+LDPC_HD void tanh_half_n(const double (&m)[n], double (&z)[n], const ExTab *tab) {
+  tanh_half_impl<n, false, false>(m, z, tab, nullptr);
+}
+// the masked form: zero[i] = the lanes (host: the flag) where m[i] is a
+// structural +-0
+template <int n>
+LDPC_HD void tanh_half_n(const double (&m)[n], double (&z)[n], const ExTab *tab,
+                         const uint64_t (&zero)[n]) {
+  tanh_half_impl<n, true, true>(m, z, tab, zero);
 }
 
 // ---------------------------------------------------------------------------
@@ -507,6 +598,29 @@ LDPC_HD double log_near1(double q) {
   const double rlo = r - rhi;
   const double rh2 = rhi * rhi;             // exact (26-bit halves)
   const double hi = fma_(rh2, kGlB[0], r);  // r + B0 rhi^2
+  const double lo = fma_(rh2, kGlB[0], r - hi);
+  const double lo2 = fma_(kGlB[0] * rlo, r + rhi, lo);
+  return fma_(poly, r3, lo2) + hi;
+}
+
+// log_near1 with the three Horner chains' first steps and W as 3-address
+// fmas (fma3_): the chains' leading constants B1, B4, B7 stay in their
+// registers across calls instead of being copied into each chain's
+// accumulator, and r is not copied for W.  The same operations on the same
+// operands in the same order.
+LDPC_HD double log_near1_lean(double q) {
+  const double r = q - 1.0;
+  const double r2 = r * r;
+  const double r3 = r * r2;
+  const double P1 = fma_(r2, kGlB[3], fma3_(kGlB[2], r, kGlB[1]));
+  const double P2 = fma_(r2, kGlB[6], fma3_(kGlB[5], r, kGlB[4]));
+  const double P3 = fma_(r3, kGlB[10], fma_(r2, kGlB[9], fma3_(kGlB[8], r, kGlB[7])));
+  const double poly = fma_(fma_(P3, r3, P2), r3, P1);
+  const double W = fma3_(0x1p27, r, r);
+  const double rhi = fma_(-0x1p27, r, W);
+  const double rlo = r - rhi;
+  const double rh2 = rhi * rhi;
+  const double hi = fma_(rh2, kGlB[0], r);
   const double lo = fma_(rh2, kGlB[0], r - hi);
   const double lo2 = fma_(kGlB[0] * rlo, r + rhi, lo);
   return fma_(poly, r3, lo2) + hi;

@@ -224,7 +224,13 @@ __device__ __forceinline__ FrameResult decode_frame(const CodeView &code, const 
       int odd = 0;
 #pragma unroll
       for (int k = 0; k < NW; ++k) odd ^= __popcll(wt.rowmask[q][k] & hard[k]);
-      w += __popcll(__builtin_amdgcn_ballot_w64((odd & 1) != 0) & row_ok[q]);
+      // the exact column-centric FIN loop keeps its zero-lane masks in scalar
+      // registers and has none to spare: a lane past M holds an all-zero row
+      // mask (wave_setup), so its parity is even and row_ok changes nothing
+      if constexpr (cols_kernel<METHOD, S, NW, DVN>() && FIN && PREC == 0)
+        w += __popcll(__builtin_amdgcn_ballot_w64((odd & 1) != 0));
+      else
+        w += __popcll(__builtin_amdgcn_ballot_w64((odd & 1) != 0) & row_ok[q]);
     }
     return w;
   };
@@ -262,6 +268,35 @@ __device__ __forceinline__ FrameResult decode_frame(const CodeView &code, const 
         ta[q][k] = e == eb_dummy ? lds_addr(tb + L.jk + lane + 64 * q) : e - kTbEb;
         ea[q][k] = (FIN && e == eb_dummy) ? lds_addr(nr + lane + 64 * q) : e;
       }
+    // exact f64, FIN: the lanes whose entry k is its column's only possible
+    // one, so its leave-one-out sum is the empty sum +0.0 in every iteration
+    // (CodeView::rowmask's tail, build_tables); tanh_half_n's masked form
+    // takes them instead of comparing every m with zero
+    constexpr bool kZeroLanes = FIN && PREC == 0;
+    uint64_t zl[NW][DVN];
+    if constexpr (kZeroLanes) {
+#pragma unroll
+      for (int q = 0; q < NW; ++q) {
+        // wave-uniform: held in scalar registers whatever load fetched them
+        uint64_t w[DVN];
+#pragma unroll
+        for (int k = 0; k < DVN; ++k) {
+          const uint64_t v = code.rowmask[M * NW + q * kDvMax + k];
+          w[k] = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+                 (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+        }
+        // records fill from entry 0, so the words of entries k >= 1 are one
+        // set, the lanes with no entry at all; their intersection is held as
+        // one scalar pair for all of them (any subset of the zero lanes is a
+        // valid mask: a zero it leaves out only takes the cold path)
+        zl[q][0] = w[0];
+        uint64_t rest = ~0ull;
+#pragma unroll
+        for (int k = 1; k < DVN; ++k) rest &= w[k];
+#pragma unroll
+        for (int k = 1; k < DVN; ++k) zl[q][k] = rest;
+      }
+    }
     Real rc[NW];
     // F64_FAST only: every check operand in tb is a tanh(m/2) with
     // |m| <= LDPC_TANH_SPLIT (so |T| < 1 and finite): the check messages need
@@ -320,7 +355,7 @@ __device__ __forceinline__ FrameResult decode_frame(const CodeView &code, const 
         // the products below consume them -- until the variable pass)
         Real Es[S];
         if constexpr (PREC == 0)
-          log_ratio_n_packed<S>(Ts, logtab, Es, tb, lane, (uint32_t)(L.ebd - L.tb));
+          log_ratio_n_packed<S, true>(Ts, logtab, Es, tb, lane, (uint32_t)(L.ebd - L.tb));
         else
           Math<PREC>::template check_msg_n<S>(Ts, logtab, Es);
 #ifdef LDPC_PATH_STATS
@@ -491,7 +526,10 @@ __device__ __forceinline__ FrameResult decode_frame(const CodeView &code, const 
 #pragma unroll
         for (int q = 0; q < NW; ++q) {
           Real th[DVN];
-          Math<PREC>::template tanh_half_n<DVN>(mv[q], th, logtab);
+          if constexpr (kZeroLanes)
+            Math<PREC>::template tanh_half_n<DVN>(mv[q], th, logtab, zl[q]);
+          else
+            Math<PREC>::template tanh_half_n<DVN>(mv[q], th, logtab);
 #pragma unroll
           for (int k = 0; k < DVN; ++k) lds_st<Real>(ta[q][k], th[k]);
         }

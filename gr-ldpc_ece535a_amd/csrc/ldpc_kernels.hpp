@@ -84,7 +84,10 @@ struct CodeView {
   const EdgeRowRec *erow;    // 64 * S records, by cell
   const EdgeColRec *ecol;    // 64 * S records, by cell
   const ColRec *cols;        // 64 * NW records by position; records >= N are all kNone
-  const uint64_t *rowmask;   // M x NW words: bit p of row j <=> H(j, column at position p)
+  const uint64_t *rowmask;   // M x NW words: bit p of row j <=> H(j, column at position p);
+                             // then NW x kDvMax words, the static zero lanes: bit l of word
+                             // q * kDvMax + k <=> entry k of position l + 64 q has no other
+                             // present entry in its column (build_tables)
   const uint16_t *lane_col;  // 64 * NW: column at position p (kNone past N)
   const uint8_t *col_lane;   // N: position of column c
   uint64_t dpos[2];          // byte g: identity cell (tb[64 S + dpos]) of 32-lane group g
