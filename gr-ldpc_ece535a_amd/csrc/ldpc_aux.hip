@@ -19,11 +19,16 @@
 //                  convention (apps/ldpc_lapack.cpp:629-636).
 //   count_errors   per-frame count of positions where two 0/1 arrays differ
 //                  (biterr, apps/ldpc_lapack.cpp:508-517, before the division).
+//   rate_match     the bytes one transmission sends of each codeword, and
+//   rate_recover   every column's Lci from the received samples of up to four
+//                  transmissions (ldpc_rate_match.hpp: puncturing, fillers, a
+//                  circular buffer, repetition), as samples any decode takes.
 //   gather_windows the windows a decoder block asks for (any start sample, either
 //                  polarity) copied out of one staged sample span into frames.
 #include <hip/hip_runtime.h>
 
 #include "ldpc_aux.hpp"
+#include "ldpc_wgframe.hpp"
 
 namespace ldpc {
 namespace {
@@ -291,6 +296,51 @@ int launch_gather_windows(const float *span, const int64_t *win, int B, int N, f
   hipLaunchKernelGGL(k_gather_windows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, span, win, total, N, out);
   return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+namespace {
+// One thread per output byte: sample e of frame b.
+__global__ void __launch_bounds__(256) k_rate_match(RmArgs rm, const uint8_t *__restrict__ cw,
+                                                    int64_t total, int N, uint8_t *__restrict__ out,
+                                                    int64_t out_stride) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int E = rm.E[0];
+  const int64_t b = t / E;
+  const int e = (int)(t - b * E);
+  out[b * out_stride + e] = cw[b * N + rm_col_of_sample(rm, rm.u0[0], e)] & 1;
+}
+
+// One thread per column: its terms gathered in the contract's order.
+__global__ void __launch_bounds__(256) k_rate_recover(RmArgs rm, const float *__restrict__ rx,
+                                                      int64_t rx_stride, float polarity,
+                                                      int64_t total, int N,
+                                                      float *__restrict__ samples) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int64_t b = t / N;
+  const int c = (int)(t - b * N);
+  const float *src = rx + b * rx_stride;
+  samples[t] = -rm_column_lci(rm, c, [&](int i) { return lci_term_of(src[i], polarity); });
+}
+}  // namespace
+
+int launch_rate_match(const RmArgs &rm, const uint8_t *cw, int B, uint8_t *out, int64_t out_stride,
+                      void *stream) {
+  const int64_t total = (int64_t)B * rm.E[0];
+  if (total <= 0) return 0;
+  hipLaunchKernelGGL(k_rate_match, dim3(blocks_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                     rm, cw, total, rm.M + rm.K, out, out_stride);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_rate_recover(const RmArgs &rm, const float *rx, int64_t rx_stride, float polarity, int B,
+                        float *samples, void *stream) {
+  const int64_t total = (int64_t)B * (rm.M + rm.K);
+  if (total <= 0) return 0;
+  hipLaunchKernelGGL(k_rate_recover, dim3(blocks_for(total, 256)), dim3(256), 0,
+                     (hipStream_t)stream, rm, rx, rx_stride, polarity, total, rm.M + rm.K, samples);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 // Stream concurrency probe (ldpc_ctx_streams): k_probe_wait spins on a flag

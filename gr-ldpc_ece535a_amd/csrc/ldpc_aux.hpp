@@ -3,6 +3,8 @@
 
 #include <stdint.h>
 
+#include "ldpc_rate_match.hpp"
+
 namespace ldpc {
 
 int launch_random_bits(uint8_t *out, int64_t n, uint64_t seed, void *stream);
@@ -21,6 +23,16 @@ int launch_encode_ira(const int32_t *rp, const int32_t *ci, int M, int K, const 
 // allowed more than 64 KiB of LDS on this device (set here on first need).
 int launch_encode_qc(const uint32_t *tab, int Z, int M, int K, int threads, int lds_bytes,
                      bool *lds_allowed, const uint8_t *data, int B, uint8_t *cw, void *stream);
+
+// Rate matching (ldpc_rate_match.hpp).  Bit selection of transmission 0 of rm:
+// out[b * out_stride + e] = bit 0 of cw[b * N + column of sample e], a thread
+// per output byte.
+int launch_rate_match(const RmArgs &rm, const uint8_t *cw, int B, uint8_t *out, int64_t out_stride,
+                      void *stream);
+// The soft combine: samples[b * N + c] = -(column c's Lci recovered from frame
+// b's received samples at rx + b * rx_stride), a thread per column.
+int launch_rate_recover(const RmArgs &rm, const float *rx, int64_t rx_stride, float polarity, int B,
+                        float *samples, void *stream);
 
 // out[b*N + i] = +-span[(win[b] >> 1) + i]: the N samples of window b, negated
 // when bit 0 of win[b] is set (the block's decode-any-window batches).

@@ -410,7 +410,7 @@ int decode_host_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, in
                      const float *in, int64_t n_in_floats, int64_t cw_stride, int elem_stride,
                      float polarity, int B, bool both, uint8_t *out_packed, uint8_t *out_bits_opt,
                      int32_t *iters_used_opt, int32_t *syn_weight_opt, float *llr_out_opt,
-                     const ldpc::LayeredArith *layered) {
+                     const ldpc::LayeredArith *layered, const ldpc::RmArgs *rm, int64_t rm_total) {
   serve_stop(ctx);
   int rc = check_decode_args(ctx, method, max_iters, et_period, precision, B, elem_stride,
                              cw_stride);
@@ -420,7 +420,9 @@ int decode_host_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, in
   if (B == 0) return LDPC_OK;
   if (!in || !out_packed) return set_err(ctx, LDPC_EINVAL, "null buffer");
   const int N = ctx->code.N, KB = ctx->code.KB;
-  const int64_t span = (int64_t)(B - 1) * cw_stride + (int64_t)(N - 1) * elem_stride + 1;
+  // a frame's samples: N of them, or what its transmissions hold
+  const int64_t n_frame = rm ? rm_total : N;
+  const int64_t span = (int64_t)(B - 1) * cw_stride + (n_frame - 1) * elem_stride + 1;
   if (span > n_in_floats) return set_err(ctx, LDPC_EINVAL, "input shorter than the frames read");
   const bool re_only = elem_stride == 2 && cw_stride % 2 == 0;
   const int64_t n_stage = re_only ? (span + 1) / 2 : span;
@@ -459,7 +461,7 @@ int decode_host_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, in
     return hip_err(ctx, e, "hipMemcpyAsync(in)");
   if (layered)
     rc = layered_device_impl(ctx, *layered, max_iters, et_period, precision, d_in, cw, es,
-                             polarity, BO, d_pk, d_bits, d_it, d_sy, d_llr, ctx->stream);
+                             polarity, BO, d_pk, d_bits, d_it, d_sy, d_llr, ctx->stream, rm);
   else
     rc = decode_device_impl(ctx, method, max_iters, et_period, precision, d_in, cw, es, polarity,
                             BO, both ? B : 0, d_pk, d_bits, d_it, d_sy, d_llr, ctx->stream);

@@ -1,7 +1,9 @@
 // ldpc_capi_encode.hip -- the C ABI of include/ldpc_hip.h: the device encoders
 // of a context (ldpc_aux.hip: small, IRA staircase, quasi-cyclic), the
 // quasi-cyclic encoder's host entry points, and the channel helpers
-// (random bits, BPSK + AWGN, bit-error counts).  Owns the context's encoder
+// (random bits, BPSK + AWGN, bit-error counts), and rate matching's device
+// entry points (the context's pattern, the bit selector behind the encoder,
+// the soft combiner in front of any decode).  Owns the context's encoder
 // group (ldpc_ctx.hpp).
 #include <stdio.h>
 
@@ -82,7 +84,78 @@ int prepare_encoder(ldpc_ctx *ctx) {
 
 }  // namespace
 
+namespace ldpc {
+namespace capi {
+
+int rate_match_args(ldpc_ctx *ctx, int n_tx, const int32_t *k0, const int32_t *e,
+                    float unreceived_lci, ldpc::RmArgs &rm, int64_t *total) {
+  std::string why;
+  if (!ldpc::rm_pattern(ctx->code.M, ctx->code.N, ctx->rm.punct, ctx->rm.filler, ctx->rm.ncb, rm,
+                        &why))
+    return set_err(ctx, LDPC_EINVAL, "bad rate-matching pattern: " + why);
+  *total = ldpc::rm_transmissions(rm, n_tx, k0, e, &why);
+  if (*total < 0) return set_err(ctx, LDPC_EINVAL, "bad transmission: " + why);
+  if (unreceived_lci != unreceived_lci)
+    return set_err(ctx, LDPC_EINVAL, "unreceived_lci must not be NaN");
+  rm.unreceived = unreceived_lci;
+  return LDPC_OK;
+}
+
+}  // namespace capi
+}  // namespace ldpc
+
 extern "C" {
+
+int ldpc_set_rate_match(ldpc_ctx *ctx, int punct, int filler, int ncb) {
+  if (!ctx) return LDPC_EINVAL;
+  ldpc::RmArgs rm;
+  std::string why;
+  if (!ldpc::rm_pattern(ctx->code.M, ctx->code.N, punct, filler, ncb, rm, &why))
+    return set_err(ctx, LDPC_EINVAL, "bad rate-matching pattern: " + why);
+  ctx->rm.punct = punct;
+  ctx->rm.filler = filler;
+  ctx->rm.ncb = ncb;
+  return LDPC_OK;
+}
+
+int ldpc_rate_match_device(ldpc_ctx *ctx, const uint8_t *d_codewords, int B, int k0, int E,
+                           uint8_t *d_out, int64_t out_stride, void *hip_stream) {
+  serve_stop(ctx);
+  if (!ctx) return LDPC_EINVAL;
+  ldpc::RmArgs rm;
+  int64_t total = 0;
+  const int32_t k0s[1] = {k0}, es[1] = {E};
+  int rc = rate_match_args(ctx, 1, k0s, es, 0.0f, rm, &total);
+  if (rc != LDPC_OK) return rc;
+  if (B < 0 || out_stride < E || (B > 0 && (!d_codewords || !d_out)))
+    return set_err(ctx, LDPC_EINVAL, "bad arguments: B >= 0, out_stride >= E, buffers given");
+  if (B == 0) return LDPC_OK;
+  hipError_t err = hipSetDevice(ctx->device);
+  if (err != hipSuccess) return hip_err(ctx, err, "hipSetDevice");
+  void *st = hip_stream ? hip_stream : (void *)ctx->stream;
+  rc = ldpc::launch_rate_match(rm, d_codewords, B, d_out, out_stride, st);
+  return rc == 0 ? LDPC_OK : hip_err(ctx, hipGetLastError(), "rate_match launch");
+}
+
+int ldpc_rate_recover_device(ldpc_ctx *ctx, const float *d_rx, int64_t rx_stride, float polarity,
+                             float unreceived_lci, int B, int n_tx, const int32_t *k0,
+                             const int32_t *e, float *d_samples_out, void *hip_stream) {
+  serve_stop(ctx);
+  if (!ctx) return LDPC_EINVAL;
+  ldpc::RmArgs rm;
+  int64_t total = 0;
+  int rc = rate_match_args(ctx, n_tx, k0, e, unreceived_lci, rm, &total);
+  if (rc != LDPC_OK) return rc;
+  if (B < 0 || rx_stride < total || (B > 0 && (!d_rx || !d_samples_out)))
+    return set_err(ctx, LDPC_EINVAL,
+                   "bad arguments: B >= 0, rx_stride >= the sum of E, buffers given");
+  if (B == 0) return LDPC_OK;
+  hipError_t err = hipSetDevice(ctx->device);
+  if (err != hipSuccess) return hip_err(ctx, err, "hipSetDevice");
+  void *st = hip_stream ? hip_stream : (void *)ctx->stream;
+  rc = ldpc::launch_rate_recover(rm, d_rx, rx_stride, polarity, B, d_samples_out, st);
+  return rc == 0 ? LDPC_OK : hip_err(ctx, hipGetLastError(), "rate_recover launch");
+}
 
 int ldpc_encode_device(ldpc_ctx *ctx, const uint8_t *d_data_bits, int B, uint8_t *d_codewords,
                        void *hip_stream) {

@@ -1,8 +1,9 @@
 // ldpc_capi_host.cc -- the part of the C ABI (include/ldpc_hip.h) that needs no
 // device: H ingestion (the constructor's matrix + reorderHMatrix,
 // lib/ldpc_decoder_cb_impl.cc:60-106), the alist parser, the reference
-// encoder, and the GF(2) recognisers the device encoder is prepared with.
-// Integer and GF(2) arithmetic only; built by the host compiler.
+// encoder, the GF(2) recognisers the device encoder is prepared with, and rate
+// matching's host forms (ldpc_rate_match.hpp).  Integer and GF(2) arithmetic,
+// and the combine's float adds; built by the host compiler.
 #include "ldpc_capi_host.hpp"
 
 #include <stdio.h>
@@ -10,6 +11,7 @@
 #include <algorithm>
 
 #include "../../include/ldpc_hip.h"
+#include "ldpc_rate_match.hpp"
 
 namespace ldpc {
 namespace capi {
@@ -323,6 +325,61 @@ int ldpc_encode(const uint8_t *Hr, int M, int N, const uint8_t *data_bits, int B
     }
     for (int j = 0; j < K; ++j) cw[M + j] = d[j] & 1;
   }
+  return LDPC_OK;
+}
+
+// Rate matching on the host (ldpc_rate_match.hpp): the plan of a call, the bit
+// selection and the soft combine, by the index functions the kernels run.
+int64_t ldpc_plan_rate_match(int M, int N, int punct, int filler, int ncb, int n_tx,
+                             const int32_t *k0, const int32_t *e, int32_t *col_out_opt,
+                             int32_t *count_out_opt) {
+  clear_create_error();
+  ldpc::RmArgs rm;
+  std::string why;
+  if (!ldpc::rm_pattern(M, N, punct, filler, ncb, rm, &why))
+    return set_create_error(LDPC_EINVAL, "bad rate-matching pattern: " + why);
+  const int64_t total = ldpc::rm_transmissions(rm, n_tx, k0, e, &why);
+  if (total < 0) return set_create_error(LDPC_EINVAL, "bad transmission: " + why);
+  ldpc::rm_plan(rm, col_out_opt, count_out_opt);
+  return total;
+}
+
+int ldpc_rate_match(int M, int N, int punct, int filler, int ncb, int k0, int E,
+                    const uint8_t *bits, int B, uint8_t *out, int64_t out_stride) {
+  clear_create_error();
+  ldpc::RmArgs rm;
+  std::string why;
+  if (!ldpc::rm_pattern(M, N, punct, filler, ncb, rm, &why))
+    return set_create_error(LDPC_EINVAL, "bad rate-matching pattern: " + why);
+  const int32_t k0s[1] = {k0}, es[1] = {E};
+  if (ldpc::rm_transmissions(rm, 1, k0s, es, &why) < 0)
+    return set_create_error(LDPC_EINVAL, "bad transmission: " + why);
+  if (B < 0 || out_stride < E || (B > 0 && (!bits || !out)))
+    return set_create_error(LDPC_EINVAL, "bad arguments: B >= 0, out_stride >= E, buffers given");
+  ldpc::rm_match(rm, bits, B, out, out_stride);
+  return LDPC_OK;
+}
+
+int ldpc_rate_recover(int M, int N, int punct, int filler, int ncb, const float *rx,
+                      int64_t n_rx_floats, int64_t rx_stride, float polarity,
+                      float unreceived_lci, int B, int n_tx, const int32_t *k0, const int32_t *e,
+                      float *samples_out) {
+  clear_create_error();
+  ldpc::RmArgs rm;
+  std::string why;
+  if (!ldpc::rm_pattern(M, N, punct, filler, ncb, rm, &why))
+    return set_create_error(LDPC_EINVAL, "bad rate-matching pattern: " + why);
+  const int64_t total = ldpc::rm_transmissions(rm, n_tx, k0, e, &why);
+  if (total < 0) return set_create_error(LDPC_EINVAL, "bad transmission: " + why);
+  if (unreceived_lci != unreceived_lci)
+    return set_create_error(LDPC_EINVAL, "unreceived_lci must not be NaN");
+  if (B < 0 || rx_stride < total || (B > 0 && (!rx || !samples_out)))
+    return set_create_error(LDPC_EINVAL,
+                            "bad arguments: B >= 0, rx_stride >= the sum of E, buffers given");
+  if (B > 0 && (int64_t)(B - 1) * rx_stride + total > n_rx_floats)
+    return set_create_error(LDPC_EINVAL, "input shorter than the frames read");
+  rm.unreceived = unreceived_lci;
+  ldpc::rm_recover(rm, rx, rx_stride, polarity, B, samples_out);
   return LDPC_OK;
 }
 

@@ -130,7 +130,8 @@ int prepare_layered(ldpc_ctx *ctx) {
     }
   const int rc = upload_layered_tables(ctx);
   if (rc != LDPC_OK) return rc;
-  lay.resident[0] = lay.resident[1] = 0;  // the kernel, its threads and bytes may differ
+  // the kernel, its threads and bytes may differ
+  lay.resident[0] = lay.resident[1] = lay.rm_resident[0] = lay.rm_resident[1] = 0;
   lay.ready = true;
   return LDPC_OK;
 }
@@ -166,7 +167,7 @@ int prepare_layered_q8(ldpc_ctx *ctx) {
   }
   const int rc = upload_layered_tables(ctx);
   if (rc != LDPC_OK) return rc;
-  lay.q8_resident = 0;
+  lay.q8_resident = lay.rm_q8_resident = 0;
   lay.q8_ready = true;
   return LDPC_OK;
 }
@@ -214,6 +215,55 @@ ldpc::LayeredArith q8_arith(int num, float llr_scale) {
   return {ldpc::kLayeredQ8, 1.0, num, llr_scale};
 }
 
+// A rate-matched layered decode of device frames: the plain decode's checks
+// (layered_device_impl repeats them: they are cheap and it is the one place
+// that states their order), then the call's transmissions.
+int rm_checked(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_iters, int et_period,
+               int precision, int64_t rx_stride, int n_tx, const int32_t *k0, const int32_t *e,
+               float unreceived_lci, int B, ldpc::RmArgs &rm, int64_t &total) {
+  serve_stop(ctx);
+  int method = LDPC_METHOD_LOGDOMAIN;
+  int rc = check_decode_args(ctx, method, max_iters, et_period, precision, B, 1, rx_stride);
+  if (rc != LDPC_OK) return rc;
+  if ((rc = layered_arith_ready(ctx, ar, precision)) != LDPC_OK) return rc;
+  if ((rc = rate_match_args(ctx, n_tx, k0, e, unreceived_lci, rm, &total)) != LDPC_OK) return rc;
+  if (rx_stride < total)
+    return set_err(ctx, LDPC_EINVAL,
+                   "rx_stride must be >= the sum of E = " + std::to_string(total) + " (got " +
+                       std::to_string(rx_stride) + ")");
+  return LDPC_OK;
+}
+
+int rm_device(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_iters, int et_period,
+              int precision, const float *d_in, int64_t rx_stride, float polarity, int n_tx,
+              const int32_t *k0, const int32_t *e, float unreceived_lci, int B,
+              uint8_t *d_out_packed, uint8_t *d_out_bits_opt, int32_t *d_iters_used_opt,
+              int32_t *d_syn_weight_opt, float *d_llr_out_opt, void *hip_stream) {
+  ldpc::RmArgs rm;
+  int64_t total = 0;
+  const int rc = rm_checked(ctx, ar, max_iters, et_period, precision, rx_stride, n_tx, k0, e,
+                            unreceived_lci, B, rm, total);
+  if (rc != LDPC_OK) return rc;
+  return layered_device_impl(ctx, ar, max_iters, et_period, precision, d_in, rx_stride, 1,
+                             polarity, B, d_out_packed, d_out_bits_opt, d_iters_used_opt,
+                             d_syn_weight_opt, d_llr_out_opt, hip_stream, &rm);
+}
+
+int rm_host(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_iters, int et_period,
+            int precision, const float *in, int64_t n_in_floats, int64_t rx_stride,
+            float polarity, int n_tx, const int32_t *k0, const int32_t *e, float unreceived_lci,
+            int B, uint8_t *out_packed, uint8_t *out_bits_opt, int32_t *iters_used_opt,
+            int32_t *syn_weight_opt, float *llr_out_opt) {
+  ldpc::RmArgs rm;
+  int64_t total = 0;
+  const int rc = rm_checked(ctx, ar, max_iters, et_period, precision, rx_stride, n_tx, k0, e,
+                            unreceived_lci, B, rm, total);
+  if (rc != LDPC_OK) return rc;
+  return decode_host_impl(ctx, LDPC_METHOD_LOGDOMAIN, max_iters, et_period, precision, in,
+                          n_in_floats, rx_stride, 1, polarity, B, false, out_packed, out_bits_opt,
+                          iters_used_opt, syn_weight_opt, llr_out_opt, &ar, &rm, total);
+}
+
 // The column degrees of a CSR H: the largest.
 int csr_dv_max(int N, int E, const int32_t *ci) {
   std::vector<int32_t> dv((size_t)N, 0);
@@ -239,7 +289,7 @@ int layered_device_impl(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_ite
                         int precision, const float *d_in, int64_t cw_stride, int elem_stride,
                         float polarity, int B, uint8_t *d_out_packed, uint8_t *d_out_bits_opt,
                         int32_t *d_iters_used_opt, int32_t *d_syn_weight_opt,
-                        float *d_llr_out_opt, void *hip_stream) {
+                        float *d_llr_out_opt, void *hip_stream, const ldpc::RmArgs *rm) {
   serve_stop(ctx);
   int method = LDPC_METHOD_LOGDOMAIN;
   int rc = check_decode_args(ctx, method, max_iters, et_period, precision, B, elem_stride,
@@ -250,7 +300,8 @@ int layered_device_impl(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_ite
   ldpc_ctx::Layered &ly = ctx->layered;
   const bool q8 = ar.kind == ldpc::kLayeredQ8, f32 = ar.kind == ldpc::kLayeredF32;
   const ldpc::LayeredLayout &lay = q8 ? ly.q8 : f32 ? ly.f32 : ly.f64;
-  int *resident = q8 ? &ly.q8_resident : &ly.resident[f32];
+  int *resident = rm ? (q8 ? &ly.rm_q8_resident : &ly.rm_resident[f32])
+                     : (q8 ? &ly.q8_resident : &ly.resident[f32]);
   if (B == 0) return LDPC_OK;
   if (!d_in || !d_out_packed) return set_err(ctx, LDPC_EINVAL, "null device buffer");
   ldpc::DecodeArgs a = make_args(d_in, cw_stride, elem_stride, polarity, B, max_iters, et_period,
@@ -273,7 +324,7 @@ int layered_device_impl(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_ite
     v.KB = code.KB;
     v.mb = ly.qc_rows;
     v.Z = code.qc_Z;
-    launched = ldpc::launch_layered_decode(v, a, lay, ar, st, resident, &advance);
+    launched = ldpc::launch_layered_decode(v, a, lay, ar, st, resident, &advance, rm);
   } else {
     ldpc::LayeredView v;
     v.rows = ly.d_rows;
@@ -285,7 +336,7 @@ int layered_device_impl(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_ite
     v.E = code.E;
     v.KB = code.KB;
     v.L = ly.L;
-    launched = ldpc::launch_layered_decode(v, a, lay, ar, st, resident, &advance);
+    launched = ldpc::launch_layered_decode(v, a, lay, ar, st, resident, &advance, rm);
   }
   if (launched != 0) return hip_err(ctx, hipGetLastError(), "kernel launch");
   commit_queue(ctx, q, advance);
@@ -397,6 +448,57 @@ int ldpc_decode_layered_device(ldpc_ctx *ctx, double scale, int max_iters, int e
                              d_in, cw_stride, elem_stride, polarity, B, d_out_packed,
                              d_out_bits_opt, d_iters_used_opt, d_syn_weight_opt, d_llr_out_opt,
                              hip_stream);
+}
+
+// The rate-matched forms: the frame load recovers the context's pattern from
+// the call's transmissions (ldpc_rate_match.hpp).  The plain decode's refusals
+// come first, then the transmissions'.
+int ldpc_decode_layered_rm(ldpc_ctx *ctx, double scale, int max_iters, int et_period,
+                           int precision, const float *in, int64_t n_in_floats, int64_t rx_stride,
+                           float polarity, int n_tx, const int32_t *k0, const int32_t *e,
+                           float unreceived_lci, int B, uint8_t *out_packed,
+                           uint8_t *out_bits_opt, int32_t *iters_used_opt,
+                           int32_t *syn_weight_opt, float *llr_out_opt) {
+  const ldpc::LayeredArith ar = float_arith(scale, precision);
+  return rm_host(ctx, ar, max_iters, et_period, precision, in, n_in_floats, rx_stride, polarity,
+                 n_tx, k0, e, unreceived_lci, B, out_packed, out_bits_opt, iters_used_opt,
+                 syn_weight_opt, llr_out_opt);
+}
+
+int ldpc_decode_layered_rm_device(ldpc_ctx *ctx, double scale, int max_iters, int et_period,
+                                  int precision, const float *d_in, int64_t rx_stride,
+                                  float polarity, int n_tx, const int32_t *k0, const int32_t *e,
+                                  float unreceived_lci, int B, uint8_t *d_out_packed,
+                                  uint8_t *d_out_bits_opt, int32_t *d_iters_used_opt,
+                                  int32_t *d_syn_weight_opt, float *d_llr_out_opt,
+                                  void *hip_stream) {
+  return rm_device(ctx, float_arith(scale, precision), max_iters, et_period, precision, d_in,
+                   rx_stride, polarity, n_tx, k0, e, unreceived_lci, B, d_out_packed,
+                   d_out_bits_opt, d_iters_used_opt, d_syn_weight_opt, d_llr_out_opt, hip_stream);
+}
+
+int ldpc_decode_layered_q8_rm(ldpc_ctx *ctx, int num, float llr_scale, int max_iters,
+                              int et_period, const float *in, int64_t n_in_floats,
+                              int64_t rx_stride, float polarity, int n_tx, const int32_t *k0,
+                              const int32_t *e, float unreceived_lci, int B, uint8_t *out_packed,
+                              uint8_t *out_bits_opt, int32_t *iters_used_opt,
+                              int32_t *syn_weight_opt, float *llr_out_opt) {
+  const ldpc::LayeredArith ar = q8_arith(num, llr_scale);
+  return rm_host(ctx, ar, max_iters, et_period, LDPC_PREC_F32, in, n_in_floats, rx_stride,
+                 polarity, n_tx, k0, e, unreceived_lci, B, out_packed, out_bits_opt,
+                 iters_used_opt, syn_weight_opt, llr_out_opt);
+}
+
+int ldpc_decode_layered_q8_rm_device(ldpc_ctx *ctx, int num, float llr_scale, int max_iters,
+                                     int et_period, const float *d_in, int64_t rx_stride,
+                                     float polarity, int n_tx, const int32_t *k0,
+                                     const int32_t *e, float unreceived_lci, int B,
+                                     uint8_t *d_out_packed, uint8_t *d_out_bits_opt,
+                                     int32_t *d_iters_used_opt, int32_t *d_syn_weight_opt,
+                                     float *d_llr_out_opt, void *hip_stream) {
+  return rm_device(ctx, q8_arith(num, llr_scale), max_iters, et_period, LDPC_PREC_F32, d_in,
+                   rx_stride, polarity, n_tx, k0, e, unreceived_lci, B, d_out_packed,
+                   d_out_bits_opt, d_iters_used_opt, d_syn_weight_opt, d_llr_out_opt, hip_stream);
 }
 
 int ldpc_plan_layers_q8(int M, int N, const int32_t *row_ptr, const int32_t *col_idx,

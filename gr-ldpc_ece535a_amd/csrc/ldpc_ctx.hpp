@@ -29,6 +29,7 @@
 #include "ldpc_kernels.hpp"
 #include "ldpc_layered.hpp"
 #include "ldpc_onchip.hpp"
+#include "ldpc_rate_match.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -205,8 +206,17 @@ struct ldpc_ctx {
     bool q8_ready = false;    // q8 is that of of_row, and the code fits
     ldpc::LayeredLayout q8{};
     int q8_resident = 0;      // workgroups the device holds of the kernel q8 selects
+    // the same of the kernels whose frame load recovers rate-matched samples
+    // (ldpc_decode_layered*_rm*): f64 / f32, q8
+    int rm_resident[2] = {0, 0}, rm_q8_resident = 0;
     void release();  // the device tables (also when a new plan replaces them)
   } layered;
+
+  // rate matching (ldpc_set_rate_match; ldpc_rate_match.hpp): the context's
+  // pattern, checked when it was set.  The default is the identity.
+  struct RateMatch {
+    int punct = 0, filler = 0, ncb = 0;
+  } rm;
 
   // device encoder (built on first ldpc_encode_device; ldpc_capi_encode.hip):
   // kind 1 small (A = H_p^-1 H_d bit rows in d_A), 2 IRA staircase, 3
@@ -382,23 +392,34 @@ int decode_device_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, 
                        float *d_llr_out_opt, void *hip_stream, const int64_t *d_win = nullptr);
 // Host-buffer decode (synchronous), staged through the pinned buffer; both:
 // the outputs are 2B frames, both polarities.  layered: the decode is a
-// layered one in that arithmetic (method unused).
+// layered one in that arithmetic (method unused).  rm (layered only): a frame is
+// rm_total rate-matched samples at cw_stride, elem_stride 1.
 int decode_host_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, int precision,
                      const float *in, int64_t n_in_floats, int64_t cw_stride, int elem_stride,
                      float polarity, int B, bool both, uint8_t *out_packed, uint8_t *out_bits_opt,
                      int32_t *iters_used_opt, int32_t *syn_weight_opt, float *llr_out_opt,
-                     const ldpc::LayeredArith *layered = nullptr);
+                     const ldpc::LayeredArith *layered = nullptr,
+                     const ldpc::RmArgs *rm = nullptr, int64_t rm_total = 0);
 
 // ---- ldpc_capi_layered.hip ----
 // What a layered decode needs beyond check_decode_args (no ring session, the
 // arithmetic's parameters, tables for the plan in force, a frame that fits).
 int layered_arith_ready(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int precision);
 // decode_device_impl for the layered kernel in the arithmetic `ar`.
+// rm: the frames are rate-matched samples, recovered by the frame load
+// (cw_stride is then rx_stride, elem_stride 1).
 int layered_device_impl(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_iters, int et_period,
                         int precision, const float *d_in, int64_t cw_stride, int elem_stride,
                         float polarity, int B, uint8_t *d_out_packed, uint8_t *d_out_bits_opt,
                         int32_t *d_iters_used_opt, int32_t *d_syn_weight_opt,
-                        float *d_llr_out_opt, void *hip_stream);
+                        float *d_llr_out_opt, void *hip_stream,
+                        const ldpc::RmArgs *rm = nullptr);
+
+// ---- ldpc_capi_encode.hip ----
+// The context's pattern and a call's transmissions, resolved into rm; *total:
+// the samples per frame.  LDPC_EINVAL with the offending value otherwise.
+int rate_match_args(ldpc_ctx *ctx, int n_tx, const int32_t *k0, const int32_t *e,
+                    float unreceived_lci, ldpc::RmArgs &rm, int64_t *total);
 
 }  // namespace capi
 }  // namespace ldpc

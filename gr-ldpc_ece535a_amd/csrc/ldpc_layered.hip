@@ -23,7 +23,9 @@
 // hence the same bits, as the scan over t != k.
 //
 // Nine kernels are one template (layered_kernel) over two choices that share
-// everything else: an arithmetic (FloatArith<double / float>, Q8Arith: the
+// everything else (and nine more with a third, the frame load: load_frame for
+// N samples in column order, load_frame_rm for rate-matched samples): an
+// arithmetic (FloatArith<double / float>, Q8Arith: the
 // types, the row's scan and message, a sample's load, the decisions) and a
 // route (TableRoute<staged / L2>, CirculantRoute: the tables, which rows a
 // thread runs in a layer and where their columns and messages are, the
@@ -483,6 +485,30 @@ __device__ __forceinline__ void load_frame(const Arith &ar, const DecodeArgs &a,
   __syncthreads();
 }
 
+// The same for a frame of rate-matched samples (ldpc_rate_match.hpp): the
+// frame is what its transmissions hold, at a.in + b * a.cw_stride, and every
+// column gathers its own terms -- the first sample of each transmission that
+// lands on it, then steps of S -- and adds them in that order.  A thread
+// strides over the columns; consecutive columns read consecutive samples up to
+// the buffer's wrap and the fillers.  No LDS beyond the frame, no atomics, and
+// the barrier that ends the load is still the only one.  (Fetching the first
+// terms of eight columns side by side, and the per-transmission words at
+// constant indices, were both measured and both lost to this loop:
+// profiles/round21/rate_match_ab_batched.txt, rate_match_ab_unrolled.txt.)
+template <typename Arith>
+__device__ __forceinline__ void load_frame_rm(const Arith &ar, const DecodeArgs &a,
+                                              const RmArgs &rm, int64_t b, int N, int E,
+                                              const LayeredLayout &lay, typename Arith::Post *LQ,
+                                              typename Arith::Msg *R) {
+  const int tid = threadIdx.x, T = blockDim.x;
+  const float pol = a.polarity;
+  const float *src = a.in + b * a.cw_stride;
+  for (int i = tid; i < N; i += T)
+    LQ[i] = ar.sample(rm_column_lci(rm, i, [&](int k) { return lci_term_of(src[k], pol); }));
+  Arith::clear(R, E, lay);
+  __syncthreads();
+}
+
 // Frame b's outputs (the syndrome's barrier is behind every LQ write): the
 // decisions into hard[N] where the arithmetic keeps them, then wg_store_frame.
 template <typename Arith>
@@ -503,9 +529,11 @@ __device__ __forceinline__ void store_frame(const DecodeArgs &a, int64_t b, int 
   wg_store_frame(a, b, M, N, KB, used, weight, bit, [&](int i) { return (float)LQ[i]; });
 }
 
-template <typename Arith, typename Route>
+// Rm: nothing (the frames are N samples in column order: load_frame), or one
+// RmArgs (the frames are rate-matched samples: load_frame_rm).
+template <typename Arith, typename Route, typename... Rm>
 __global__ void __launch_bounds__(kLayeredMaxThreads)
-    layered_kernel(typename Route::View gv, DecodeArgs a, LayeredLayout lay, Arith ar) {
+    layered_kernel(typename Route::View gv, DecodeArgs a, LayeredLayout lay, Arith ar, Rm... rm) {
   using Post = typename Arith::Post;
   using Msg = typename Arith::Msg;
   extern __shared__ __align__(16) unsigned char smem[];
@@ -519,7 +547,10 @@ __global__ void __launch_bounds__(kLayeredMaxThreads)
 
   int64_t b = blockIdx.x;
   while (b < a.B) {
-    load_frame(ar, a, b, gv.N, gv.E, lay, LQ, R);
+    if constexpr (sizeof...(Rm) == 0)
+      load_frame(ar, a, b, gv.N, gv.E, lay, LQ, R);
+    else
+      load_frame_rm(ar, a, rm..., b, gv.N, gv.E, lay, LQ, R);
     int used = 0, weight = 0;
     for (int h = 0;; ++h) {
       route.rewind();
@@ -542,47 +573,56 @@ __global__ void __launch_bounds__(kLayeredMaxThreads)
 
 // ---- the launch ------------------------------------------------------------------
 
-template <typename Arith, typename Route>
+template <typename Arith, typename Route, typename... Rm>
 int launch_kernel(const typename Route::View &g, DecodeArgs a, const LayeredLayout &lay, Arith ar,
-                  hipStream_t st, int &resident, uint32_t *advance_out) {
-  if (!wg_launch((const void *)layered_kernel<Arith, Route>, lay.threads, lay.total, resident, a,
-                 advance_out))
+                  hipStream_t st, int &resident, uint32_t *advance_out, Rm... rm) {
+  if (!wg_launch((const void *)layered_kernel<Arith, Route, Rm...>, lay.threads, lay.total,
+                 resident, a, advance_out))
     return -3;
-  hipLaunchKernelGGL((layered_kernel<Arith, Route>), dim3((unsigned)a.waves),
-                     dim3((unsigned)lay.threads), (size_t)lay.total, st, g, a, lay, ar);
+  hipLaunchKernelGGL((layered_kernel<Arith, Route, Rm...>), dim3((unsigned)a.waves),
+                     dim3((unsigned)lay.threads), (size_t)lay.total, st, g, a, lay, ar, rm...);
   return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+template <typename Route, typename... Rm>
+int launch_arith(const typename Route::View &g, const DecodeArgs &args, const LayeredLayout &lay,
+                 const LayeredArith &ar, hipStream_t st, int *resident, uint32_t *advance_out,
+                 Rm... rm) {
+  if (ar.kind == kLayeredQ8)
+    return launch_kernel<Q8Arith, Route>(g, args, lay, {ar.num, ar.llr_scale}, st, *resident,
+                                         advance_out, rm...);
+  if (ar.kind == kLayeredF32)
+    return launch_kernel<FloatArith<float>, Route>(g, args, lay, {(float)ar.scale}, st, *resident,
+                                                   advance_out, rm...);
+  return launch_kernel<FloatArith<double>, Route>(g, args, lay, {ar.scale}, st, *resident,
+                                                  advance_out, rm...);
 }
 
 template <typename Route>
 int launch_route(const typename Route::View &g, const DecodeArgs &args, const LayeredLayout &lay,
-                 const LayeredArith &ar, void *stream, int *resident, uint32_t *advance_out) {
+                 const LayeredArith &ar, void *stream, int *resident, uint32_t *advance_out,
+                 const RmArgs *rm) {
   *advance_out = 0;
   if (args.B <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (ar.kind == kLayeredQ8)
-    return launch_kernel<Q8Arith, Route>(g, args, lay, {ar.num, ar.llr_scale}, st, *resident,
-                                         advance_out);
-  if (ar.kind == kLayeredF32)
-    return launch_kernel<FloatArith<float>, Route>(g, args, lay, {(float)ar.scale}, st, *resident,
-                                                   advance_out);
-  return launch_kernel<FloatArith<double>, Route>(g, args, lay, {ar.scale}, st, *resident,
-                                                  advance_out);
+  return rm ? launch_arith<Route>(g, args, lay, ar, st, resident, advance_out, *rm)
+            : launch_arith<Route>(g, args, lay, ar, st, resident, advance_out);
 }
 
 }  // namespace
 
 int launch_layered_decode(const LayeredView &g, const DecodeArgs &args, const LayeredLayout &lay,
                           const LayeredArith &ar, void *stream, int *resident,
-                          uint32_t *advance_out) {
-  return lay.staged ? launch_route<TableRoute<true>>(g, args, lay, ar, stream, resident, advance_out)
-                    : launch_route<TableRoute<false>>(g, args, lay, ar, stream, resident,
-                                                      advance_out);
+                          uint32_t *advance_out, const RmArgs *rm) {
+  return lay.staged
+             ? launch_route<TableRoute<true>>(g, args, lay, ar, stream, resident, advance_out, rm)
+             : launch_route<TableRoute<false>>(g, args, lay, ar, stream, resident, advance_out, rm);
 }
 
 int launch_layered_decode(const LayeredQcView &g, const DecodeArgs &args, const LayeredLayout &lay,
                           const LayeredArith &ar, void *stream, int *resident,
-                          uint32_t *advance_out) {
-  return launch_route<CirculantRoute>(g, args, lay, ar, stream, resident, advance_out);
+                          uint32_t *advance_out, const RmArgs *rm) {
+  return launch_route<CirculantRoute>(g, args, lay, ar, stream, resident, advance_out, rm);
 }
 
 }  // namespace ldpc

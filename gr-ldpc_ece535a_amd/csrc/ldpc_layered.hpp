@@ -11,6 +11,7 @@
 
 #include "ldpc_kernels.hpp"
 #include "ldpc_layers.hpp"
+#include "ldpc_rate_match.hpp"
 
 namespace ldpc {
 
@@ -49,16 +50,18 @@ struct LayeredArith {
 // here: the resident workgroups).  *advance_out: what the launch adds to its
 // counter.  *resident: the workgroups the device holds of the kernel this
 // arithmetic and layout select (0: not looked up yet).  Returns 0, or -3 on a
-// launch error.
+// launch error.  rm: the frames are rate-matched samples (ldpc_rate_match.hpp)
+// and the frame load recovers them -- args.cw_stride is the frames' stride,
+// args.elem_stride 1; a kernel of its own, so `resident` is that kernel's.
 int launch_layered_decode(const LayeredView &g, const DecodeArgs &args, const LayeredLayout &lay,
                           const LayeredArith &ar, void *stream, int *resident,
-                          uint32_t *advance_out);
+                          uint32_t *advance_out, const RmArgs *rm = nullptr);
 
 // The same for a quasi-cyclic code decoded by its block rows: `lay` is the
 // layout for mb layers of Z rows with nothing staged (lay.total == lay.frame:
 // the base tables are read through the scalar cache).
 int launch_layered_decode(const LayeredQcView &g, const DecodeArgs &args, const LayeredLayout &lay,
                           const LayeredArith &ar, void *stream, int *resident,
-                          uint32_t *advance_out);
+                          uint32_t *advance_out, const RmArgs *rm = nullptr);
 
 }  // namespace ldpc

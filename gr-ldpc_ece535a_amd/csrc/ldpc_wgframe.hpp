@@ -30,6 +30,15 @@ __device__ __forceinline__ float lci_of(float in, float polarity) {
   return -tx;
 }
 
+// The same as a term of a sum (rate matching's combine, ldpc_rate_match.hpp):
+// the negated value in a register of its own, so that the add takes -tx and
+// not a subtraction of tx -- the same value, but a NaN's sign would differ.
+__device__ __forceinline__ float lci_term_of(float in, float polarity) {
+  float v = lci_of(in, polarity);
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
 // Frame b's first sample and polarity: a window of a list (DecodeArgs::win),
 // or strided frames whose second half, in a both-polarities launch
 // (DecodeArgs::pm_half), re-reads the first half's frames negated.

@@ -14,7 +14,7 @@ from ._capi import (  # noqa: F401
     FLAG_NO_REORDER, FLAG_QC_TABLES, METHOD_BITFLIP, METHOD_HARD, METHOD_LOGDOMAIN, METHOD_SUMPRODUCT,
     PREC_F32, PREC_F64, PREC_F64_FAST, PREC_F64_LIBM, Decoder, LdpcError, bpsk_awgn, check_frame, count_bit_errors,
     default_h, encode, encode_qc, plan_layers, plan_layers_q8, plan_layout, plan_qc, plan_qc_encoder, plan_qc_q8,
-    random_bits, reorder_h,
+    plan_rate_match, random_bits, rate_match, rate_recover, reorder_h,
 )
 from .blocks import (  # noqa: F401,E402
     STATE_IN_SYNC, STATE_IN_SYNC_INVERTED, STATE_OUT_OF_SYNC, ldpc_decoder_cb, ldpc_encoder_bc,

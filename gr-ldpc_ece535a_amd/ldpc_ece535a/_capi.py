@@ -104,7 +104,30 @@ SIGNATURES = {
                                     ctypes.c_float, _i, _u8p, _u8p, _i32p, _i32p, _f32p]),
     "ldpc_decode_layered_q8_device": (_i, [_vp, _i, ctypes.c_float, _i, _i, _vp, _i64, _i,
                                            ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldpc_plan_rate_match": (_i64, [_i, _i, _i, _i, _i, _i, _i32p, _i32p, _i32p, _i32p]),
+    "ldpc_rate_match": (_i, [_i, _i, _i, _i, _i, _i, _i, _u8p, _i, _u8p, _i64]),
+    "ldpc_rate_recover": (_i, [_i, _i, _i, _i, _i, _f32p, _i64, _i64, ctypes.c_float,
+                               ctypes.c_float, _i, _i, _i32p, _i32p, _f32p]),
+    "ldpc_set_rate_match": (_i, [_vp, _i, _i, _i]),
+    "ldpc_rate_match_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp]),
+    "ldpc_rate_recover_device": (_i, [_vp, _vp, _i64, ctypes.c_float, ctypes.c_float, _i, _i,
+                                      _i32p, _i32p, _vp, _vp]),
+    "ldpc_decode_layered_rm": (_i, [_vp, ctypes.c_double, _i, _i, _i, _f32p, _i64, _i64,
+                                    ctypes.c_float, _i, _i32p, _i32p, ctypes.c_float, _i, _u8p,
+                                    _u8p, _i32p, _i32p, _f32p]),
+    "ldpc_decode_layered_rm_device": (_i, [_vp, ctypes.c_double, _i, _i, _i, _vp, _i64,
+                                           ctypes.c_float, _i, _i32p, _i32p, ctypes.c_float, _i,
+                                           _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldpc_decode_layered_q8_rm": (_i, [_vp, _i, ctypes.c_float, _i, _i, _f32p, _i64, _i64,
+                                       ctypes.c_float, _i, _i32p, _i32p, ctypes.c_float, _i, _u8p,
+                                       _u8p, _i32p, _i32p, _f32p]),
+    "ldpc_decode_layered_q8_rm_device": (_i, [_vp, _i, ctypes.c_float, _i, _i, _vp, _i64,
+                                              ctypes.c_float, _i, _i32p, _i32p, ctypes.c_float, _i,
+                                              _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+
+RM_MAX_TX = 4
+UNRECEIVED_LCI = 2.0 ** -100   # what a column no sample reaches gets, by default
 
 _lib = None
 
@@ -332,6 +355,72 @@ def encode_qc(base, Z, data_bits):
     out = np.zeros((d.shape[0], nb * Z), np.uint8)
     _check(lib().ldpc_encode_qc(mb, nb, Z, _p(base, _i32p), _p(d, _u8p), d.shape[0],
                                 _p(out, _u8p)))
+    return out
+
+
+_tx_memo = {}
+
+
+def _tx_arrays(tx):
+    """A call's transmissions [(k0, E), ...] as two C int32 arrays and the sum
+    of E.  Kept per list: a decode call per batch would otherwise spend more
+    time building them than the launch takes."""
+    key = tuple((int(k0), int(e)) for k0, e in tx)
+    hit = _tx_memo.get(key)
+    if hit is None:
+        if len(_tx_memo) >= 64:
+            _tx_memo.clear()
+        arr = ctypes.c_int32 * len(key)
+        hit = _tx_memo[key] = (arr(*[k0 for k0, _ in key]), arr(*[e for _, e in key]),
+                               sum(max(e, 0) for _, e in key))
+    return hit
+
+
+def plan_rate_match(M, N, punct, filler, ncb, tx):
+    """ldpc_plan_rate_match (host only, no GPU): the pattern (punct, filler,
+    ncb) on an M x N code and the transmissions tx = [(k0, E), ...] of one
+    call.  dict with total (the samples per frame, sum E), col (total,) = the
+    column of every sample, and count (N,) = the samples that reach each
+    column, -1 for a filler.  Raises LDPC_EINVAL, the message naming the
+    offending value, for what include/ldpc_hip.h refuses."""
+    k0, e, n = _tx_arrays(tx)
+    col = np.zeros(max(n, 1), np.int32)
+    count = np.zeros(max(int(N), 1), np.int32)
+    total = _check(lib().ldpc_plan_rate_match(int(M), int(N), int(punct), int(filler), int(ncb),
+                                              len(k0), k0, e,
+                                              _p(col, _i32p), _p(count, _i32p)))
+    return dict(total=int(total), col=col[:total], count=count[:N])
+
+
+def rate_match(M, N, punct, filler, ncb, k0, E, bits):
+    """ldpc_rate_match (host only, no GPU): the bit selection of one
+    transmission, (B, N) codeword bytes -> (B, E) bytes."""
+    bits = np.ascontiguousarray(np.atleast_2d(bits), np.uint8)
+    if bits.shape[1] != N:
+        raise LdpcError("LDPC_EINVAL: bits must be (B, N)")
+    out = np.zeros((bits.shape[0], max(int(E), 1)), np.uint8)
+    _check(lib().ldpc_rate_match(int(M), int(N), int(punct), int(filler), int(ncb), int(k0),
+                                 int(E), _p(bits, _u8p), bits.shape[0], _p(out, _u8p),
+                                 out.shape[1]))
+    return out[:, :int(E)]
+
+
+def rate_recover(M, N, punct, filler, ncb, tx, rx, polarity=1.0, unreceived_lci=UNRECEIVED_LCI,
+                 rx_stride=None, B=None):
+    """ldpc_rate_recover (host only, no GPU): the soft combine of the received
+    samples rx (frame b's transmissions concatenated at b * rx_stride) into
+    (B, N) samples y = -Lci, which any decode takes at polarity 1."""
+    k0, e, n = _tx_arrays(tx)
+    x = np.ascontiguousarray(rx, np.float32).reshape(-1)
+    if rx_stride is None:
+        rx_stride = n
+    if B is None:
+        B = x.size // rx_stride if rx_stride else 0
+    out = np.zeros((B, int(N)), np.float32)
+    _check(lib().ldpc_rate_recover(int(M), int(N), int(punct), int(filler), int(ncb),
+                                   _p(x, _f32p), x.size, int(rx_stride), float(polarity),
+                                   float(unreceived_lci), int(B), len(k0), k0,
+                                   e, _p(out, _f32p)))
     return out
 
 
@@ -683,6 +772,110 @@ class Decoder:
                                                    int(cw_stride), int(elem_stride),
                                                    float(polarity), int(B), d_packed, d_bits,
                                                    d_iters, d_synd, d_llr, stream), self._ctx)
+
+    def set_rate_match(self, punct=0, filler=0, ncb=0):
+        """ldpc_set_rate_match: the context's rate-matching pattern
+        (include/ldpc_hip.h): transmit positions [0, punct) are never sent, the
+        last `filler` information bits are known zeros and never sent, and the
+        circular buffer is positions [punct, punct + ncb) (ncb = 0: to the
+        end).  (0, 0, 0), the default, is the identity.  A refused pattern
+        raises and leaves the current one in force."""
+        _check(lib().ldpc_set_rate_match(self._ctx, int(punct), int(filler), int(ncb)), self._ctx)
+
+    def rate_match_device(self, d_codewords, B, k0, E, d_out, out_stride=None, stream=None):
+        """ldpc_rate_match_device: the E bytes transmission (k0, E) sends of
+        each of B device codewords (B, N), frame b's at d_out + b * out_stride
+        (default E)."""
+        _check(lib().ldpc_rate_match_device(self._ctx, d_codewords, int(B), int(k0), int(E), d_out,
+                                            int(E if out_stride is None else out_stride), stream),
+               self._ctx)
+
+    def rate_recover_device(self, d_rx, B, tx, d_samples, polarity=1.0,
+                            unreceived_lci=UNRECEIVED_LCI, rx_stride=None, stream=None):
+        """ldpc_rate_recover_device: the soft combine of B frames of received
+        samples (the transmissions tx = [(k0, E), ...] concatenated, frame b at
+        d_rx + b * rx_stride floats, default sum E) into (B, N) device samples
+        y = -Lci, which any decode of this context takes at polarity 1."""
+        k0, e, n = _tx_arrays(tx)
+        _check(lib().ldpc_rate_recover_device(self._ctx, d_rx,
+                                              int(n if rx_stride is None else rx_stride),
+                                              float(polarity), float(unreceived_lci), int(B),
+                                              len(k0), k0, e, d_samples,
+                                              stream), self._ctx)
+
+    def _rm_host(self, fn, head, rx, tx, max_iters, et_period, polarity, unreceived_lci,
+                 rx_stride, B, want_bits, want_llr):
+        k0, e, n = _tx_arrays(tx)
+        x = np.ascontiguousarray(rx, np.float32).reshape(-1)
+        if rx_stride is None:
+            rx_stride = n
+        if B is None:
+            B = x.size // rx_stride if rx_stride else 0
+        packed = np.zeros((B, self.KB), np.uint8)
+        bits = np.zeros((B, self.N), np.uint8) if want_bits else None
+        iters = np.zeros(B, np.int32)
+        synd = np.zeros(B, np.int32)
+        post = np.zeros((B, self.N), np.float32) if want_llr else None
+        _check(fn(self._ctx, *head, _p(x, _f32p), x.size, int(rx_stride), float(polarity),
+                  len(k0), k0, e, float(unreceived_lci), int(B),
+                  _p(packed, _u8p), _p(bits, _u8p), _p(iters, _i32p), _p(synd, _i32p),
+                  _p(post, _f32p)), self._ctx)
+        out = dict(packed=packed, iters=iters, synd=synd)
+        if want_bits:
+            out["bits"] = bits
+        if want_llr:
+            out["llr"] = post
+        return out
+
+    def decode_layered_rm(self, rx, tx, scale=1.0, max_iters=50, et_period=1, precision=PREC_F64,
+                          polarity=1.0, unreceived_lci=UNRECEIVED_LCI, rx_stride=None, B=None,
+                          want_bits=True, want_llr=False):
+        """ldpc_decode_layered_rm: decode_layered of rate-matched host samples:
+        frame b is the transmissions tx = [(k0, E), ...] of the context's
+        pattern (set_rate_match) concatenated at b * rx_stride floats (default
+        sum E), recovered by the kernel's frame load.  unreceived_lci is the
+        Lci of a column no sample reaches: the default 2**-100 breaks the
+        float contract's sign(0) = 0 tie, with which (0.0 is legal) a punctured
+        column silences its rows."""
+        head = (float(scale), int(max_iters), int(et_period), int(precision))
+        return self._rm_host(lib().ldpc_decode_layered_rm, head, rx, tx, max_iters, et_period,
+                             polarity, unreceived_lci, rx_stride, B, want_bits, want_llr)
+
+    def decode_layered_q8_rm(self, rx, tx, num=16, llr_scale=8.0, max_iters=50, et_period=1,
+                             polarity=1.0, unreceived_lci=UNRECEIVED_LCI, rx_stride=None, B=None,
+                             want_bits=True, want_llr=False):
+        """ldpc_decode_layered_q8_rm: decode_layered_q8 of rate-matched host
+        samples, as decode_layered_rm (a filler quantises to +127, an
+        unreceived column to 0)."""
+        head = (int(num), float(llr_scale), int(max_iters), int(et_period))
+        return self._rm_host(lib().ldpc_decode_layered_q8_rm, head, rx, tx, max_iters, et_period,
+                             polarity, unreceived_lci, rx_stride, B, want_bits, want_llr)
+
+    def decode_layered_rm_device(self, d_rx, B, tx, d_packed, scale=1.0, max_iters=50,
+                                 et_period=1, precision=PREC_F64, polarity=1.0,
+                                 unreceived_lci=UNRECEIVED_LCI, rx_stride=None, d_bits=None,
+                                 d_iters=None, d_synd=None, d_llr=None, stream=None):
+        """ldpc_decode_layered_rm_device: enqueue decode_layered_rm on
+        device-resident buffers (raw pointers / ints)."""
+        k0, e, n = _tx_arrays(tx)
+        _check(lib().ldpc_decode_layered_rm_device(
+            self._ctx, float(scale), int(max_iters), int(et_period), int(precision), d_rx,
+            int(n if rx_stride is None else rx_stride), float(polarity), len(k0), k0,
+            e, float(unreceived_lci), int(B), d_packed, d_bits, d_iters, d_synd, d_llr,
+            stream), self._ctx)
+
+    def decode_layered_q8_rm_device(self, d_rx, B, tx, d_packed, num=16, llr_scale=8.0,
+                                    max_iters=50, et_period=1, polarity=1.0,
+                                    unreceived_lci=UNRECEIVED_LCI, rx_stride=None, d_bits=None,
+                                    d_iters=None, d_synd=None, d_llr=None, stream=None):
+        """ldpc_decode_layered_q8_rm_device: enqueue decode_layered_q8_rm on
+        device-resident buffers."""
+        k0, e, n = _tx_arrays(tx)
+        _check(lib().ldpc_decode_layered_q8_rm_device(
+            self._ctx, int(num), float(llr_scale), int(max_iters), int(et_period), d_rx,
+            int(n if rx_stride is None else rx_stride), float(polarity), len(k0), k0,
+            e, float(unreceived_lci), int(B), d_packed, d_bits, d_iters, d_synd, d_llr,
+            stream), self._ctx)
 
     def set_launch_mode(self, mode):
         """MODE_LATENCY (default: one decode at a time) or MODE_THROUGHPUT

@@ -22,6 +22,8 @@ private copies.
                                [--ebn0 -7:10:0.5] [--code default|dvbs2] [--json out]
                                [--qc MC,ME,NB,Z,DEG,SEED | --qc dual:MB,NB,Z,DEG,SEED]
                                [--layered SCALE] [--layered-q8 NUM[:LLR_SCALE]]
+                               [--rate-match PUNCT,FILLER,NCB --tx K0:E[,K0:E...]
+                                [--unreceived-lci LCI]]
 
 --qc sweeps a quasi-cyclic code in place of --code: codes.qc_parity_core (a
 dual-diagonal core of MC block rows and ME extension rows, the 802.11n /
@@ -38,6 +40,19 @@ variant (ldpc_decode_layered_q8_device) at factor NUM / 16, the samples scaled
 by LLR_SCALE (default 8) before they are rounded.  Neither is one of the
 reference's decoders; without the options the output is the reference
 program's four curves.
+
+--rate-match PUNCT,FILLER,NCB with --tx K0:E[,K0:E...] sweeps the code as it is
+sent (include/ldpc_hip.h, "Rate matching"): the last FILLER information bits
+are zeroed before the encoder, the codewords go through ldpc_rate_match_device
+once per transmission (up to four), every transmitted sample gets noise of its
+own, the layered curves decode what was received with the fused entry points
+(ldpc_decode_layered*_rm_device) and the reference's four decoders take the
+output of ldpc_rate_recover_device.  BER is still counted over all N codeword
+bits, the unsent ones included, and sigma_of keeps the reference's noise
+convention: sqrt(N0) from Eb/N0 alone, with no code-rate term, so a point of a
+rate-matched sweep is not the Eb/N0 of the code as sent.  The JSON says both.
+--unreceived-lci is what a column no sample reaches enters the decoders with
+(default 2^-100, the binding's).
 """
 import argparse
 import json
@@ -60,11 +75,19 @@ def sigma_of(ebn0_db):
     return math.sqrt(1.0 / math.exp(ebn0_db * math.log(10.0) / 10.0))
 
 
+RATE_MATCH_NOTE = ("BER over all N codeword bits, the unsent ones included; sigma = sqrt(N0) from "
+                   "Eb/N0 alone (the reference's convention): no code-rate term")
+
+
 def sweep(dec=None, ebn0=DEFAULT_EBN0, frames=30, iterations=5, seed=0, precision=0, device=0,
-          layered_scale=None, layered_q8=None):
+          layered_scale=None, layered_q8=None, rate_match=None, tx=None,
+          unreceived_lci=_capi.UNRECEIVED_LCI):
     """Returns {method name: {"ber": [...], "fer": [...]}} over `ebn0`; with
     layered_scale also LAYERED, the layered min-sum decoder at that scale; with
-    layered_q8 = (num, llr_scale) also LAYERED_Q8, the fixed-point one."""
+    layered_q8 = (num, llr_scale) also LAYERED_Q8, the fixed-point one.  With
+    rate_match = (punct, filler, ncb) and tx = [(k0, E), ...] the frames are sent
+    rate-matched (see the module's docstring), a column no sample reaches
+    entering every decoder with unreceived_lci."""
     import torch
     if dec is None:
         dec = _capi.Decoder(device=device)
@@ -79,19 +102,51 @@ def sweep(dec=None, ebn0=DEFAULT_EBN0, frames=30, iterations=5, seed=0, precisio
     d_err = torch.empty(B, dtype=torch.int32, device=dev)
     stream = torch.cuda.Stream(dev)
     sp = stream.cuda_stream
+    if rate_match is not None:
+        if not tx:
+            raise ValueError("rate_match needs tx = [(k0, E), ...]")
+        dec.set_rate_match(*rate_match)
+        filler, total = int(rate_match[1]), sum(int(e) for _, e in tx)
+        d_sent = torch.empty((B, total), dtype=torch.uint8, device=dev)
+        d_rx = torch.empty((B, total), dtype=torch.float32, device=dev)
     runs = (list(METHODS) + ([(LAYERED, None)] if layered_scale is not None else []) +
             ([(LAYERED_Q8, None)] if layered_q8 is not None else []))
     out = {name: {"ber": [], "fer": []} for name, _ in runs}
     for i, db in enumerate(ebn0):
         s0 = (int(seed) * 1000003 + i) & 0xFFFFFFFF
         _capi.random_bits(d_data.data_ptr(), B * K, s0, sp)
+        if rate_match is not None and filler:
+            with torch.cuda.stream(stream):
+                d_data[:, K - filler:] = 0
         dec.encode_device(d_data.data_ptr(), B, d_cw.data_ptr(), sp)
-        _capi.bpsk_awgn(d_cw.data_ptr(), B * N, sigma_of(db), s0 ^ 0x5DEECE66D, d_tx.data_ptr(),
-                        sp)
+        if rate_match is None:
+            _capi.bpsk_awgn(d_cw.data_ptr(), B * N, sigma_of(db), s0 ^ 0x5DEECE66D,
+                            d_tx.data_ptr(), sp)
+        else:
+            off = 0
+            for k0, e in tx:
+                dec.rate_match_device(d_cw.data_ptr(), B, k0, e, d_sent.data_ptr() + off,
+                                      out_stride=total, stream=sp)
+                off += int(e)
+            # one draw per transmitted sample: every transmission has its own noise
+            _capi.bpsk_awgn(d_sent.data_ptr(), B * total, sigma_of(db), s0 ^ 0x5DEECE66D,
+                            d_rx.data_ptr(), sp)
+            # what the reference's decoders take: the combined samples, in column order
+            dec.rate_recover_device(d_rx.data_ptr(), B, tx, d_tx.data_ptr(),
+                                    unreceived_lci=unreceived_lci, stream=sp)
         for name, m in runs:
             kw = dict(max_iters=iterations, precision=precision, d_bits=d_bits.data_ptr(),
                       d_synd=d_synd.data_ptr(), stream=sp)
-            if name == LAYERED_Q8:
+            if rate_match is not None and name == LAYERED_Q8:
+                del kw["precision"]
+                dec.decode_layered_q8_rm_device(d_rx.data_ptr(), B, tx, d_packed.data_ptr(),
+                                                num=layered_q8[0], llr_scale=layered_q8[1],
+                                                unreceived_lci=unreceived_lci, **kw)
+            elif rate_match is not None and m is None:
+                dec.decode_layered_rm_device(d_rx.data_ptr(), B, tx, d_packed.data_ptr(),
+                                             scale=layered_scale, unreceived_lci=unreceived_lci,
+                                             **kw)
+            elif name == LAYERED_Q8:
                 del kw["precision"]
                 dec.decode_layered_q8_device(d_tx.data_ptr(), B, d_packed.data_ptr(),
                                              num=layered_q8[0], llr_scale=layered_q8[1], **kw)
@@ -183,7 +238,29 @@ def main(argv=None):
     ap.add_argument("--layered-q8", default=None, metavar="NUM[:LLR_SCALE]",
                     help="add the fixed-point layered min-sum decoder at factor NUM / 16 "
                          "(NUM in 1..16), samples scaled by LLR_SCALE (default 8)")
+    ap.add_argument("--rate-match", default=None, metavar="PUNCT,FILLER,NCB",
+                    help="send the code rate-matched: PUNCT leading positions never sent, FILLER "
+                         "known-zero information bits, a circular buffer of NCB positions (0: "
+                         "to the end); needs --tx")
+    ap.add_argument("--tx", default=None, metavar="K0:E[,K0:E...]",
+                    help="the transmissions of a rate-matched frame (up to four): E samples "
+                         "from buffer offset K0 each, combined by the receiver")
+    ap.add_argument("--unreceived-lci", type=float, default=_capi.UNRECEIVED_LCI, metavar="LCI",
+                    help="with --rate-match: the Lci of a column no sample reaches (default "
+                         "2^-100; 2^-10 keeps the float decoders' later iterations alive, see "
+                         "DESIGN section 7f)")
     a = ap.parse_args(argv)
+    rate_match = tx = None
+    if (a.rate_match is None) != (a.tx is None):
+        ap.error("--rate-match and --tx go together")
+    if a.rate_match is not None:
+        try:
+            rate_match = tuple(int(x) for x in a.rate_match.split(","))
+            tx = [tuple(int(x) for x in t.split(":")) for t in a.tx.split(",")]
+            if len(rate_match) != 3 or any(len(t) != 2 for t in tx):
+                raise ValueError
+        except ValueError:
+            ap.error("--rate-match takes PUNCT,FILLER,NCB and --tx K0:E[,K0:E...]")
     q8 = None
     if a.layered_q8 is not None:
         num, _, sc = a.layered_q8.partition(":")
@@ -205,11 +282,17 @@ def main(argv=None):
         dec = _capi.Decoder()
     grid = parse_range(a.ebn0)
     res = sweep(dec, grid, a.frames, a.iterations, a.seed, a.precision, layered_scale=a.layered,
-                layered_q8=q8)
+                layered_q8=q8, rate_match=rate_match, tx=tx, unreceived_lci=a.unreceived_lci)
     sys.stdout.write(octave(grid, res))
     if a.json:
-        json.dump({"ebn0": grid, "frames": a.frames, "iterations": a.iterations,
-                   "code": code, "results": res}, open(a.json, "w"), indent=1)
+        doc = {"ebn0": grid, "frames": a.frames, "iterations": a.iterations, "code": code,
+               "results": res}
+        if rate_match is not None:
+            doc["rate_match"] = {"punct": rate_match[0], "filler": rate_match[1],
+                                 "ncb": rate_match[2], "tx": [list(t) for t in tx],
+                                 "unreceived_lci": a.unreceived_lci,
+                                 "note": RATE_MATCH_NOTE}
+        json.dump(doc, open(a.json, "w"), indent=1)
     return 0
 
 

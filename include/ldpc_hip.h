@@ -553,6 +553,128 @@ int ldpc_decode_layered_q8_device(ldpc_ctx *ctx, int num, float llr_scale, int m
                                   int32_t *d_syn_weight_opt, float *d_llr_out_opt,
                                   void *hip_stream);
 
+/* Rate matching: puncturing, shortening (filler bits), a circular buffer read
+ * from a start k0 with wrap-around and repetition, and the soft combining of
+ * several transmissions (HARQ), for the layered decoders and, through
+ * ldpc_rate_recover_device, for every other decode.
+ *
+ * Transmit order.  Parity is in columns 0..M-1 and information in M..N-1 (K =
+ * N - M).  Transmit position p in [0, N) is column M + p for p < K (systematic
+ * first) and column p - K otherwise.
+ *
+ * The pattern of a context, ldpc_set_rate_match(ctx, punct, filler, ncb):
+ * positions [0, punct) are never sent; positions [K - filler, K) are known
+ * zeros and never sent; the circular buffer is positions [punct, punct + ncb),
+ * ncb = 0 meaning N - punct.  Required, else LDPC_EINVAL with the offending
+ * value in the message: punct >= 0, filler >= 0, punct <= K - filler, K <=
+ * punct + ncb <= N, S = ncb - filler >= 1.  (0, 0, 0) is the default and the
+ * identity: every position sent once, in transmit order.  Nothing is assumed
+ * about a lifting size; the pattern works on any context.
+ *
+ * A transmission (k0, E), 0 <= k0 < ncb and 1 <= E <= 16 S, walks the buffer
+ * offsets k0, k0 + 1, ... mod ncb, skipping the fillers, until E positions are
+ * emitted.  In closed form, with fs = K - filler - punct and fe = K - punct:
+ *   u0 = (k0 < fs ? k0 : max(k0, fe) - filler) mod S
+ *   sample e has compact index u = (u0 + e) mod S, buffer offset
+ *   j = u < fs ? u : u + filler, and position punct + j.
+ * A k0 inside the fillers starts at the first position behind them.  A call
+ * takes 1 <= n_tx <= LDPC_RM_MAX_TX transmissions; frame b holds them
+ * concatenated at in + b * rx_stride, contiguous floats, rx_stride >= sum E.
+ *
+ * Recovery.  Every sample contributes its Lci as every decode takes it: tx =
+ * in * polarity, then negated.  A column's terms are taken with transmissions
+ * ascending and, within one, e ascending: the first as it is, every later one
+ * one float add -- a fixed order, so the sum is bit-reproducible (a gather per
+ * column; no atomics).  A non-filler column that no sample reaches gets
+ * `unreceived_lci` (not NaN); a filler column gets +INFINITY, which decides 0.
+ * The result enters the decoder where a sample's Lci does: (Real)Lci for the
+ * float layered decoder; scaled, rounded and clamped for q8, where a filler
+ * becomes +127 and an unreceived column 0.  Everything after the load is the
+ * layered contract above, unchanged.
+ *
+ * unreceived_lci.  The float contract keeps sign(0) = 0 and multiplies a row's
+ * whole sign product into every message, so a row with an exactly-zero input
+ * sends zero to every column, the erased one included: with 0.0 a punctured
+ * column never recovers and its rows stay silent.  A tiny positive value such
+ * as 2^-100 (the Python binding's default) breaks the tie without weighing on
+ * any minimum, and the first iteration recovers the column.  It is absorbed by
+ * the first real message, though (m + 2^-100 = m): a column whose posterior
+ * then rests on one row's message gives that row q = m - m = 0 in the next
+ * iteration and goes back to 0.  A value that survives the add, such as 2^-10,
+ * keeps later iterations working over unsent columns (DESIGN section 7f has
+ * the figures).  0.0 stays legal.  q8 has sign(0) = +1 and needs nothing: any
+ * such value quantises to 0.
+ *
+ *   ldpc_plan_rate_match   (no GPU) checks a pattern on an M x N code and a
+ *                          call's transmissions; col_out_opt[sum E] receives
+ *                          the column of every sample, count_out_opt[N] the
+ *                          samples that reach each column (-1 for a filler).
+ *                          Returns sum E, or LDPC_EINVAL.
+ *   ldpc_rate_match        (no GPU) bit selection: bits (B, N) bytes -> out,
+ *                          frame b's E bytes (bit 0 of each source byte) at
+ *                          out + b * out_stride.
+ *   ldpc_rate_recover      (no GPU) the combine: rx as above -> samples_out
+ *                          (B, N), y = -Lci.  Decoding y at polarity 1 on any
+ *                          entry point equals the fused decodes below.
+ *   ldpc_set_rate_match    the context's pattern (kept until set again).
+ *   ldpc_rate_match_device   ldpc_rate_match with the context's pattern on
+ *                          device buffers, behind ldpc_encode_device; one
+ *                          thread per output byte.
+ *   ldpc_rate_recover_device ldpc_rate_recover with the context's pattern on
+ *                          device buffers, one thread per column: what gives
+ *                          every other decode of this library rate matching.
+ *   ldpc_decode_layered_rm, _rm_device, ldpc_decode_layered_q8_rm,
+ *   _q8_rm_device          the layered decodes with the recovery fused into
+ *                          the frame load: their plain counterparts'
+ *                          arguments with rx_stride in place of cw_stride, no
+ *                          elem_stride, and (n_tx, k0, e, unreceived_lci)
+ *                          added.  The host forms stage sum E floats per
+ *                          frame.  Refusals: the plain decode's, then the
+ *                          transmissions', a NaN unreceived_lci and rx_stride
+ *                          < sum E (LDPC_EINVAL). */
+#define LDPC_RM_MAX_TX 4
+int64_t ldpc_plan_rate_match(int M, int N, int punct, int filler, int ncb, int n_tx,
+                             const int32_t *k0, const int32_t *e, int32_t *col_out_opt,
+                             int32_t *count_out_opt);
+int ldpc_rate_match(int M, int N, int punct, int filler, int ncb, int k0, int E,
+                    const uint8_t *bits, int B, uint8_t *out, int64_t out_stride);
+int ldpc_rate_recover(int M, int N, int punct, int filler, int ncb, const float *rx,
+                      int64_t n_rx_floats, int64_t rx_stride, float polarity,
+                      float unreceived_lci, int B, int n_tx, const int32_t *k0, const int32_t *e,
+                      float *samples_out);
+int ldpc_set_rate_match(ldpc_ctx *ctx, int punct, int filler, int ncb);
+int ldpc_rate_match_device(ldpc_ctx *ctx, const uint8_t *d_codewords, int B, int k0, int E,
+                           uint8_t *d_out, int64_t out_stride, void *hip_stream);
+int ldpc_rate_recover_device(ldpc_ctx *ctx, const float *d_rx, int64_t rx_stride, float polarity,
+                             float unreceived_lci, int B, int n_tx, const int32_t *k0,
+                             const int32_t *e, float *d_samples_out, void *hip_stream);
+int ldpc_decode_layered_rm(ldpc_ctx *ctx, double scale, int max_iters, int et_period,
+                           int precision, const float *in, int64_t n_in_floats, int64_t rx_stride,
+                           float polarity, int n_tx, const int32_t *k0, const int32_t *e,
+                           float unreceived_lci, int B, uint8_t *out_packed,
+                           uint8_t *out_bits_opt, int32_t *iters_used_opt,
+                           int32_t *syn_weight_opt, float *llr_out_opt);
+int ldpc_decode_layered_rm_device(ldpc_ctx *ctx, double scale, int max_iters, int et_period,
+                                  int precision, const float *d_in, int64_t rx_stride,
+                                  float polarity, int n_tx, const int32_t *k0, const int32_t *e,
+                                  float unreceived_lci, int B, uint8_t *d_out_packed,
+                                  uint8_t *d_out_bits_opt, int32_t *d_iters_used_opt,
+                                  int32_t *d_syn_weight_opt, float *d_llr_out_opt,
+                                  void *hip_stream);
+int ldpc_decode_layered_q8_rm(ldpc_ctx *ctx, int num, float llr_scale, int max_iters,
+                              int et_period, const float *in, int64_t n_in_floats,
+                              int64_t rx_stride, float polarity, int n_tx, const int32_t *k0,
+                              const int32_t *e, float unreceived_lci, int B, uint8_t *out_packed,
+                              uint8_t *out_bits_opt, int32_t *iters_used_opt,
+                              int32_t *syn_weight_opt, float *llr_out_opt);
+int ldpc_decode_layered_q8_rm_device(ldpc_ctx *ctx, int num, float llr_scale, int max_iters,
+                                     int et_period, const float *d_in, int64_t rx_stride,
+                                     float polarity, int n_tx, const int32_t *k0,
+                                     const int32_t *e, float unreceived_lci, int B,
+                                     uint8_t *d_out_packed, uint8_t *d_out_bits_opt,
+                                     int32_t *d_iters_used_opt, int32_t *d_syn_weight_opt,
+                                     float *d_llr_out_opt, void *hip_stream);
+
 /* The frame ring: ONE persistent launch decodes every batch posted to it
  * (small codes; min-sum and sum-product, any precision).  The frames of all
  * posted batches form one device queue, so a wave that finishes a frame of
