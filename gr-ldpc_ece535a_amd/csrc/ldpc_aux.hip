@@ -23,6 +23,9 @@
 //   rate_recover   every column's Lci from the received samples of up to four
 //                  transmissions (ldpc_rate_match.hpp: puncturing, fillers, a
 //                  circular buffer, repetition), as samples any decode takes.
+//   crc_attach     a payload's CRC behind it, in front of any encoder, and
+//   crc_check      the remainder of a decode's packed information bits
+//                  (ldpc_crc.hpp), one wave per frame.
 //   gather_windows the windows a decoder block asks for (any start sample, either
 //                  polarity) copied out of one staged sample span into frames.
 #include <hip/hip_runtime.h>
@@ -340,6 +343,70 @@ int launch_rate_recover(const RmArgs &rm, const float *rx, int64_t rx_stride, fl
   if (total <= 0) return 0;
   hipLaunchKernelGGL(k_rate_recover, dim3(blocks_for(total, 256)), dim3(256), 0,
                      (hipStream_t)stream, rm, rx, rx_stride, polarity, total, rm.M + rm.K, samples);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The code-block CRC (ldpc_crc.hpp), one wave per frame over the weights
+// w[p] = x^(A-1-p) mod g that the layered kernels check with: a lane strides
+// over the positions, selects with a mask and the wave folds its lanes.
+namespace {
+__device__ __forceinline__ uint32_t wave_xor(uint32_t x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x ^= (uint32_t)__shfl_xor((int)x, m, 64);
+  return x;
+}
+
+// payload (B, A - len) -> info (B, K): the payload, its CRC MSB first, zeros.
+__global__ void __launch_bounds__(64) k_crc_attach(const uint32_t *__restrict__ w, int len, int A,
+                                                   int K, const uint8_t *__restrict__ payload,
+                                                   uint8_t *__restrict__ info) {
+  const int lane = threadIdx.x, P = A - len;
+  const uint8_t *src = payload + (int64_t)blockIdx.x * P;
+  uint8_t *dst = info + (int64_t)blockIdx.x * K;
+  uint32_t x = 0;
+  for (int p = lane; p < P; p += 64) {
+    const uint32_t bit = src[p] & 1u;
+    dst[p] = (uint8_t)bit;
+    x ^= w[p] & (0u - bit);
+  }
+  x = wave_xor(x);
+  if (lane < len) dst[P + lane] = (uint8_t)((x >> (len - 1 - lane)) & 1u);
+  for (int p = A + lane; p < K; p += 64) dst[p] = 0;
+}
+
+// packed (B, KB), information bits MSB first -> rem[b]: a lane per byte.
+__global__ void __launch_bounds__(64) k_crc_check(const uint32_t *__restrict__ w, int A, int KB,
+                                                  const uint8_t *__restrict__ packed,
+                                                  uint32_t *__restrict__ rem) {
+  const int lane = threadIdx.x;
+  const uint8_t *src = packed + (int64_t)blockIdx.x * KB;
+  uint32_t x = 0;
+  for (int q = lane; 8 * q < A; q += 64) {
+    const uint32_t by = src[q];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int p = 8 * q + j;
+      if (p < A) x ^= w[p] & (0u - ((by >> (7 - j)) & 1u));
+    }
+  }
+  x = wave_xor(x);
+  if (lane == 0) rem[blockIdx.x] = x;
+}
+}  // namespace
+
+int launch_crc_attach(const uint32_t *w, int len, int A, int K, const uint8_t *payload, int B,
+                      uint8_t *info, void *stream) {
+  if (B <= 0) return 0;
+  hipLaunchKernelGGL(k_crc_attach, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, w, len, A,
+                     K, payload, info);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_crc_check(const uint32_t *w, int A, int KB, const uint8_t *packed, int B, uint32_t *rem,
+                     void *stream) {
+  if (B <= 0) return 0;
+  hipLaunchKernelGGL(k_crc_check, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, w, A, KB,
+                     packed, rem);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

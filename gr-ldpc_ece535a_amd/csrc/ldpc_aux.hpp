@@ -34,6 +34,15 @@ int launch_rate_match(const RmArgs &rm, const uint8_t *cw, int B, uint8_t *out, 
 int launch_rate_recover(const RmArgs &rm, const float *rx, int64_t rx_stride, float polarity, int B,
                         float *samples, void *stream);
 
+// The code-block CRC (ldpc_crc.hpp), w: the A weights on the device.  Attach:
+// payload (B, A - len) bytes -> info (B, K) bytes (payload, CRC, zero fillers),
+// what the encoders take.  Check: rem[b] = the remainder of the block in
+// packed (B, KB), a decode's packed information bits.  One wave per frame.
+int launch_crc_attach(const uint32_t *w, int len, int A, int K, const uint8_t *payload, int B,
+                      uint8_t *info, void *stream);
+int launch_crc_check(const uint32_t *w, int A, int KB, const uint8_t *packed, int B, uint32_t *rem,
+                     void *stream);
+
 // out[b*N + i] = +-span[(win[b] >> 1) + i]: the N samples of window b, negated
 // when bit 0 of win[b] is set (the block's decode-any-window batches).
 int launch_gather_windows(const float *span, const int64_t *win, int B, int N, float *out,

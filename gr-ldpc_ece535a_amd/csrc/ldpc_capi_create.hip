@@ -462,6 +462,7 @@ void ldpc_destroy(ldpc_ctx *ctx) {
   ctx->queues.release();
   ctx->onchip.release();
   ctx->layered.release();
+  ctx->crc.release();
   ctx->graph.release();
   ctx->encoder.release();
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

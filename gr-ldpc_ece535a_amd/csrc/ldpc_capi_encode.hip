@@ -112,10 +112,49 @@ int ldpc_set_rate_match(ldpc_ctx *ctx, int punct, int filler, int ncb) {
   std::string why;
   if (!ldpc::rm_pattern(ctx->code.M, ctx->code.N, punct, filler, ncb, rm, &why))
     return set_err(ctx, LDPC_EINVAL, "bad rate-matching pattern: " + why);
+  // the CRC's block is what the fillers leave: it must stay longer than the
+  // CRC, and its weights are those of the new length
+  if (ctx->crc.len > 0) {
+    const int rc = crc_upload(ctx, ctx->crc.len, ctx->crc.poly, filler);
+    if (rc != LDPC_OK) return rc;
+  }
   ctx->rm.punct = punct;
   ctx->rm.filler = filler;
   ctx->rm.ncb = ncb;
   return LDPC_OK;
+}
+
+int ldpc_crc_attach_device(ldpc_ctx *ctx, const uint8_t *d_payload, int B, uint8_t *d_info_out,
+                           void *hip_stream) {
+  serve_stop(ctx);
+  if (!ctx) return LDPC_EINVAL;
+  const ldpc_ctx::Crc &c = ctx->crc;
+  if (c.len == 0) return set_err(ctx, LDPC_EINVAL, "no CRC is set (ldpc_set_crc)");
+  if (B < 0 || (B > 0 && (!d_payload || !d_info_out)))
+    return set_err(ctx, LDPC_EINVAL, "bad arguments: B >= 0, buffers given");
+  if (B == 0) return LDPC_OK;
+  hipError_t err = hipSetDevice(ctx->device);
+  if (err != hipSuccess) return hip_err(ctx, err, "hipSetDevice");
+  void *st = hip_stream ? hip_stream : (void *)ctx->stream;
+  const int rc = ldpc::launch_crc_attach(c.d_w, c.len, c.A, ctx->code.N - ctx->code.M, d_payload, B,
+                                         d_info_out, st);
+  return rc == 0 ? LDPC_OK : hip_err(ctx, hipGetLastError(), "crc_attach launch");
+}
+
+int ldpc_crc_check_device(ldpc_ctx *ctx, const uint8_t *d_packed, int B, uint32_t *d_rem_out,
+                          void *hip_stream) {
+  serve_stop(ctx);
+  if (!ctx) return LDPC_EINVAL;
+  const ldpc_ctx::Crc &c = ctx->crc;
+  if (c.len == 0) return set_err(ctx, LDPC_EINVAL, "no CRC is set (ldpc_set_crc)");
+  if (B < 0 || (B > 0 && (!d_packed || !d_rem_out)))
+    return set_err(ctx, LDPC_EINVAL, "bad arguments: B >= 0, buffers given");
+  if (B == 0) return LDPC_OK;
+  hipError_t err = hipSetDevice(ctx->device);
+  if (err != hipSuccess) return hip_err(ctx, err, "hipSetDevice");
+  void *st = hip_stream ? hip_stream : (void *)ctx->stream;
+  const int rc = ldpc::launch_crc_check(c.d_w, c.A, ctx->code.KB, d_packed, B, d_rem_out, st);
+  return rc == 0 ? LDPC_OK : hip_err(ctx, hipGetLastError(), "crc_check launch");
 }
 
 int ldpc_rate_match_device(ldpc_ctx *ctx, const uint8_t *d_codewords, int B, int k0, int E,

@@ -1,8 +1,9 @@
 // ldpc_capi_host.cc -- the part of the C ABI (include/ldpc_hip.h) that needs no
 // device: H ingestion (the constructor's matrix + reorderHMatrix,
 // lib/ldpc_decoder_cb_impl.cc:60-106), the alist parser, the reference
-// encoder, the GF(2) recognisers the device encoder is prepared with, and rate
-// matching's host forms (ldpc_rate_match.hpp).  Integer and GF(2) arithmetic,
+// encoder, the GF(2) recognisers the device encoder is prepared with, rate
+// matching's host forms (ldpc_rate_match.hpp) and the code-block CRC's
+// (ldpc_crc.hpp).  Integer and GF(2) arithmetic,
 // and the combine's float adds; built by the host compiler.
 #include "ldpc_capi_host.hpp"
 
@@ -11,6 +12,7 @@
 #include <algorithm>
 
 #include "../../include/ldpc_hip.h"
+#include "ldpc_crc.hpp"
 #include "ldpc_rate_match.hpp"
 
 namespace ldpc {
@@ -380,6 +382,40 @@ int ldpc_rate_recover(int M, int N, int punct, int filler, int ncb, const float 
     return set_create_error(LDPC_EINVAL, "input shorter than the frames read");
   rm.unreceived = unreceived_lci;
   ldpc::rm_recover(rm, rx, rx_stride, polarity, B, samples_out);
+  return LDPC_OK;
+}
+
+// The code-block CRC on the host (ldpc_crc.hpp): the register, the block and
+// its weights, and the attach, by the text ldpc_set_crc builds its table with.
+int64_t ldpc_crc_bits(int len, uint32_t poly, const uint8_t *bits, int64_t n) {
+  clear_create_error();
+  std::string why;
+  if (!ldpc::crc_check(len, poly, &why)) return set_create_error(LDPC_EINVAL, "bad CRC: " + why);
+  if (n < 0 || (n > 0 && !bits))
+    return set_create_error(LDPC_EINVAL, "bad arguments: n >= 0, bits given");
+  return (int64_t)ldpc::crc_bits(len, poly, bits, n);
+}
+
+int ldpc_plan_crc(int M, int N, int filler, int len, uint32_t poly, uint32_t *weights_out_opt) {
+  clear_create_error();
+  std::string why;
+  if (!ldpc::crc_check(len, poly, &why)) return set_create_error(LDPC_EINVAL, "bad CRC: " + why);
+  const int A = ldpc::crc_block(M, N, filler, len, &why);
+  if (A < 0) return set_create_error(LDPC_EINVAL, "bad CRC: " + why);
+  if (weights_out_opt) ldpc::crc_weights(len, poly, A, weights_out_opt);
+  return A;
+}
+
+int ldpc_crc_attach(int M, int N, int filler, int len, uint32_t poly, const uint8_t *payload,
+                    int B, uint8_t *info_out) {
+  clear_create_error();
+  std::string why;
+  if (!ldpc::crc_check(len, poly, &why)) return set_create_error(LDPC_EINVAL, "bad CRC: " + why);
+  const int A = ldpc::crc_block(M, N, filler, len, &why);
+  if (A < 0) return set_create_error(LDPC_EINVAL, "bad CRC: " + why);
+  if (B < 0 || (B > 0 && (!payload || !info_out)))
+    return set_create_error(LDPC_EINVAL, "bad arguments: B >= 0, buffers given");
+  ldpc::crc_attach(len, poly, A, N - M, payload, B, info_out);
   return LDPC_OK;
 }
 

@@ -20,6 +20,12 @@ void ldpc_ctx::Layered::release() {
   tabs = false;
 }
 
+void ldpc_ctx::Crc::release() {
+  free_device(d_w);
+  free_device(d_rem);
+  rem_cap = last_B = 0;
+}
+
 namespace {
 
 int largest_layer(const std::vector<int32_t> &layer_of_row, int L) {
@@ -132,6 +138,7 @@ int prepare_layered(ldpc_ctx *ctx) {
   if (rc != LDPC_OK) return rc;
   // the kernel, its threads and bytes may differ
   lay.resident[0] = lay.resident[1] = lay.rm_resident[0] = lay.rm_resident[1] = 0;
+  for (int *r : ctx->crc.resident) r[ldpc::kLayeredF64] = r[ldpc::kLayeredF32] = 0;
   lay.ready = true;
   return LDPC_OK;
 }
@@ -168,6 +175,7 @@ int prepare_layered_q8(ldpc_ctx *ctx) {
   const int rc = upload_layered_tables(ctx);
   if (rc != LDPC_OK) return rc;
   lay.q8_resident = lay.rm_q8_resident = 0;
+  for (int *r : ctx->crc.resident) r[ldpc::kLayeredQ8] = 0;
   lay.q8_ready = true;
   return LDPC_OK;
 }
@@ -310,6 +318,15 @@ int layered_device_impl(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_ite
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
   void *st = hip_stream ? hip_stream : (void *)ctx->stream;
+  // while a CRC is set the decode is the kernel that checks it, and frame b's
+  // remainder goes to word b of the context's array
+  ldpc::CrcArgs crc_args{}, *crc = nullptr;
+  if (ctx->crc.len > 0) {
+    if ((rc = crc_results_room(ctx, B)) != LDPC_OK) return rc;
+    crc_args = {ctx->crc.d_w, ctx->crc.A, code.M, ctx->crc.mode == LDPC_CRC_STOP, ctx->crc.d_rem};
+    crc = &crc_args;
+    resident = &ctx->crc.resident[rm ? 1 : 0][ar.kind];
+  }
   size_t q = 0;
   if ((rc = bind_queue(ctx, st, max_iters, a, q)) != LDPC_OK) return rc;
   uint32_t advance = 0;
@@ -324,7 +341,7 @@ int layered_device_impl(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_ite
     v.KB = code.KB;
     v.mb = ly.qc_rows;
     v.Z = code.qc_Z;
-    launched = ldpc::launch_layered_decode(v, a, lay, ar, st, resident, &advance, rm);
+    launched = ldpc::launch_layered_decode(v, a, lay, ar, st, resident, &advance, rm, crc);
   } else {
     ldpc::LayeredView v;
     v.rows = ly.d_rows;
@@ -336,10 +353,60 @@ int layered_device_impl(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_ite
     v.E = code.E;
     v.KB = code.KB;
     v.L = ly.L;
-    launched = ldpc::launch_layered_decode(v, a, lay, ar, st, resident, &advance, rm);
+    launched = ldpc::launch_layered_decode(v, a, lay, ar, st, resident, &advance, rm, crc);
   }
   if (launched != 0) return hip_err(ctx, hipGetLastError(), "kernel launch");
   commit_queue(ctx, q, advance);
+  if (crc) {
+    ctx->crc.last_B = B;
+    ctx->crc.last_stream = st;
+  }
+  return LDPC_OK;
+}
+
+int crc_upload(ldpc_ctx *ctx, int len, uint32_t poly, int filler) {
+  std::string why;
+  if (!ldpc::crc_check(len, poly, &why)) return set_err(ctx, LDPC_EINVAL, "bad CRC: " + why);
+  const int A = ldpc::crc_block(ctx->code.M, ctx->code.N, filler, len, &why);
+  if (A < 0) return set_err(ctx, LDPC_EINVAL, "bad CRC: " + why);
+  ldpc_ctx::Crc &c = ctx->crc;
+  if (c.d_w && c.w_len == len && c.poly == poly && c.A == A) {
+    c.len = len;
+    return LDPC_OK;
+  }
+  std::vector<uint32_t> w((size_t)A);
+  ldpc::crc_weights(len, poly, A, w.data());
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
+  // decodes that read the previous weights may still run (any stream)
+  if (c.d_w && (e = hipDeviceSynchronize()) != hipSuccess)
+    return hip_err(ctx, e, "hipDeviceSynchronize");
+  uint32_t *d_w = nullptr;
+  const char *what = nullptr;
+  if (!upload(&d_w, w, "upload(CRC weights)", what, e)) {
+    free_device(d_w);
+    return hip_err(ctx, e, what);
+  }
+  free_device(c.d_w);
+  c.d_w = d_w;
+  c.len = c.w_len = len;
+  c.poly = poly;
+  c.A = A;
+  c.last_B = 0;
+  return LDPC_OK;
+}
+
+int crc_results_room(ldpc_ctx *ctx, int B) {
+  ldpc_ctx::Crc &c = ctx->crc;
+  if (B <= c.rem_cap) return LDPC_OK;
+  // the decode before this one may still write the array that goes
+  hipError_t e = c.d_rem ? hipDeviceSynchronize() : hipSuccess;
+  if (e != hipSuccess) return hip_err(ctx, e, "hipDeviceSynchronize");
+  free_device(c.d_rem);
+  c.rem_cap = c.last_B = 0;
+  if ((e = hipMalloc((void **)&c.d_rem, (size_t)B * 4)) != hipSuccess)
+    return hip_err(ctx, e, "hipMalloc(CRC results)");
+  c.rem_cap = B;
   return LDPC_OK;
 }
 
@@ -499,6 +566,48 @@ int ldpc_decode_layered_q8_rm_device(ldpc_ctx *ctx, int num, float llr_scale, in
   return rm_device(ctx, q8_arith(num, llr_scale), max_iters, et_period, LDPC_PREC_F32, d_in,
                    rx_stride, polarity, n_tx, k0, e, unreceived_lci, B, d_out_packed,
                    d_out_bits_opt, d_iters_used_opt, d_syn_weight_opt, d_llr_out_opt, hip_stream);
+}
+
+// The code-block CRC of the layered decodes (ldpc_crc.hpp): the context's CRC
+// and the remainders of its last decode.
+int ldpc_set_crc(ldpc_ctx *ctx, int len, uint32_t poly, int mode) {
+  if (!ctx) return LDPC_EINVAL;
+  if (len == 0) {
+    ctx->crc.len = 0;
+    ctx->crc.last_B = 0;
+    return LDPC_OK;
+  }
+  if (mode != LDPC_CRC_REPORT && mode != LDPC_CRC_STOP)
+    return set_err(ctx, LDPC_EINVAL,
+                   "mode must be LDPC_CRC_REPORT or LDPC_CRC_STOP (got " + std::to_string(mode) + ")");
+  // a refused CRC leaves the one in force as it is
+  const int rc = crc_upload(ctx, len, poly, ctx->rm.filler);
+  if (rc != LDPC_OK) return rc;
+  ctx->crc.mode = mode;
+  ctx->crc.last_B = 0;
+  return LDPC_OK;
+}
+
+int ldpc_crc_results(ldpc_ctx *ctx, uint32_t *out, int n) {
+  if (!ctx) return LDPC_EINVAL;
+  const ldpc_ctx::Crc &c = ctx->crc;
+  if (c.len == 0) return set_err(ctx, LDPC_EINVAL, "no CRC is set (ldpc_set_crc)");
+  if (n < 0 || n > c.last_B || (n > 0 && !out))
+    return set_err(ctx, LDPC_EINVAL,
+                   "n must be in [0, " + std::to_string(c.last_B) +
+                       "], the frames of the last layered decode (got " + std::to_string(n) + ")");
+  if (n == 0) return LDPC_OK;
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
+  hipStream_t st = (hipStream_t)c.last_stream;
+  if ((e = hipMemcpyAsync(out, c.d_rem, (size_t)n * 4, hipMemcpyDeviceToHost, st)) != hipSuccess)
+    return hip_err(ctx, e, "hipMemcpyAsync(CRC results)");
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_err(ctx, e, "hipStreamSynchronize");
+  return LDPC_OK;
+}
+
+const uint32_t *ldpc_crc_results_device(const ldpc_ctx *ctx) {
+  return ctx && ctx->crc.len > 0 && ctx->crc.last_B > 0 ? ctx->crc.d_rem : nullptr;
 }
 
 int ldpc_plan_layers_q8(int M, int N, const int32_t *row_ptr, const int32_t *col_idx,

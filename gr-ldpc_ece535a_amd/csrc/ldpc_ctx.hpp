@@ -25,6 +25,7 @@
 
 #include "../../include/ldpc_hip.h"
 #include "ldpc_capi_host.hpp"
+#include "ldpc_crc.hpp"
 #include "ldpc_graph.hpp"
 #include "ldpc_kernels.hpp"
 #include "ldpc_layered.hpp"
@@ -217,6 +218,24 @@ struct ldpc_ctx {
   struct RateMatch {
     int punct = 0, filler = 0, ncb = 0;
   } rm;
+
+  // the code-block CRC (ldpc_set_crc; ldpc_crc.hpp; ldpc_capi_layered.hip):
+  // len == 0 is off.  The weights of the A block positions on the device (d_w,
+  // those of (w_len, poly, A): they outlive an off, so that turning the same
+  // CRC on again is host work), rebuilt when another CRC or another filler
+  // count is set; the remainders
+  // of the last layered decode (d_rem, grown with B), its frames and stream;
+  // and the workgroups the device holds of the layered kernels that check it
+  // ([rate-matched][arithmetic]).
+  struct Crc {
+    int len = 0, mode = 0, A = 0, w_len = 0;
+    uint32_t poly = 0;
+    uint32_t *d_w = nullptr, *d_rem = nullptr;
+    int rem_cap = 0, last_B = 0;
+    void *last_stream = nullptr;
+    int resident[2][3] = {{0, 0, 0}, {0, 0, 0}};
+    void release();
+  } crc;
 
   // device encoder (built on first ldpc_encode_device; ldpc_capi_encode.hip):
   // kind 1 small (A = H_p^-1 H_d bit rows in d_A), 2 IRA staircase, 3
@@ -414,6 +433,12 @@ int layered_device_impl(ldpc_ctx *ctx, const ldpc::LayeredArith &ar, int max_ite
                         int32_t *d_iters_used_opt, int32_t *d_syn_weight_opt,
                         float *d_llr_out_opt, void *hip_stream,
                         const ldpc::RmArgs *rm = nullptr);
+// Checks (len, poly) and the block A = K - filler > len, then builds and
+// uploads the A weights and makes them the context's CRC (its mode stays).
+// LDPC_EINVAL with the offending value, and nothing changed, otherwise.
+int crc_upload(ldpc_ctx *ctx, int len, uint32_t poly, int filler);
+// Room for B remainders in the context's result array.
+int crc_results_room(ldpc_ctx *ctx, int B);
 
 // ---- ldpc_capi_encode.hip ----
 // The context's pattern and a call's transmissions, resolved into rm; *total:

@@ -24,7 +24,9 @@
 //
 // Nine kernels are one template (layered_kernel) over two choices that share
 // everything else (and nine more with a third, the frame load: load_frame for
-// N samples in column order, load_frame_rm for rate-matched samples): an
+// N samples in column order, load_frame_rm for rate-matched samples; and each
+// of the eighteen once more with the code-block CRC of ldpc_crc.hpp checked
+// beside the syndrome): an
 // arithmetic (FloatArith<double / float>, Q8Arith: the
 // types, the row's scan and message, a sample's load, the decisions) and a
 // route (TableRoute<staged / L2>, CirculantRoute: the tables, which rows a
@@ -36,6 +38,7 @@
 
 #include <algorithm>
 #include <limits>
+#include <type_traits>
 
 #include "ldpc_dispatch.hpp"
 #include "ldpc_layered.hpp"
@@ -529,8 +532,72 @@ __device__ __forceinline__ void store_frame(const DecodeArgs &a, int64_t b, int 
   wg_store_frame(a, b, M, N, KB, used, weight, bit, [&](int i) { return (float)LQ[i]; });
 }
 
-// Rm: nothing (the frames are N samples in column order: load_frame), or one
-// RmArgs (the frames are rate-matched samples: load_frame_rm).
+// ---- the code-block CRC ----------------------------------------------------------
+
+// The kernel's trailing arguments, by type: an RmArgs, a CrcArgs, both in that
+// order, or neither.
+template <typename... X>
+constexpr bool kHasRm = (std::is_same_v<X, RmArgs> || ...);
+template <typename... X>
+constexpr bool kHasCrc = (std::is_same_v<X, CrcArgs> || ...);
+template <typename... X>
+__device__ __forceinline__ const RmArgs &rm_of(const RmArgs &rm, const X &...) {
+  return rm;
+}
+__device__ __forceinline__ const CrcArgs &crc_of(const CrcArgs &c) { return c; }
+__device__ __forceinline__ const CrcArgs &crc_of(const RmArgs &, const CrcArgs &c) { return c; }
+
+// A wave's share of the block's remainder (ldpc_crc.hpp) into the workgroup's
+// CRC bytes: the XOR of w[p] over the block positions p whose decision is 1,
+// the workgroup's threads striding over p and selecting with a mask, folded
+// over the wave's lanes.  The posteriors are read where they are, in LDS; the
+// weights through the constant address space (written before the launch,
+// never during it).  No barrier: the syndrome's, which follows, is behind
+// these writes, and the next check's writes are behind a layer's.
+//
+// (Eight strides' reads batched side by side and the wave folded through DPP
+// and four lane reads was measured and did not beat this loop:
+// profiles/round22/crc_ab_batched.txt.  The loop is not unrolled: unrolled by
+// the compiler the batched form spilled some 200 registers.)
+template <typename Arith>
+__device__ __forceinline__ void crc_wave_share(const CrcArgs &c, const typename Arith::Post *LQ,
+                                               int *red) {
+  const int tid = threadIdx.x, T = blockDim.x;
+  QcWords w = qc_words(c.w);
+  const typename Arith::Post *info = LQ + c.M;
+  uint32_t x = 0;
+#pragma unroll 1
+  for (int p = tid; p < c.A; p += T) x ^= w[p] & (0u - (uint32_t)Arith::decision(info[p]));
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x ^= (uint32_t)__shfl_xor((int)x, m, 64);
+  if ((tid & 63) == 0) {
+    uint8_t *by = reinterpret_cast<uint8_t *>(red + kWgRedCrc) + 3 * (tid >> 6);
+    by[0] = (uint8_t)x;
+    by[1] = (uint8_t)(x >> 8);
+    by[2] = (uint8_t)(x >> 16);
+  }
+}
+
+// The workgroup's remainder from its CRC bytes, behind a barrier: every thread
+// gets it.  Sixteen 3-byte records in twelve words, those of absent waves zero
+// since the launch: the words are folded four records at a time, then the four.
+__device__ __forceinline__ uint32_t crc_remainder(const int *red) {
+  const uint32_t *v = reinterpret_cast<const uint32_t *>(red + kWgRedCrc);
+  uint32_t a0 = 0, a1 = 0, a2 = 0;
+#pragma unroll
+  for (int j = 0; j < kWgRedCrcWords; j += 3) {
+    a0 ^= v[j];
+    a1 ^= v[j + 1];
+    a2 ^= v[j + 2];
+  }
+  return (a0 & 0xffffffu) ^ ((a0 >> 24) | ((a1 & 0xffffu) << 8)) ^
+         ((a1 >> 16) | ((a2 & 0xffu) << 16)) ^ (a2 >> 8);
+}
+
+// Rm: nothing (the frames are N samples in column order: load_frame), one
+// RmArgs (the frames are rate-matched samples: load_frame_rm), one CrcArgs
+// (the block's remainder is checked beside the syndrome and stored with the
+// frame), or an RmArgs and a CrcArgs.
 template <typename Arith, typename Route, typename... Rm>
 __global__ void __launch_bounds__(kLayeredMaxThreads)
     layered_kernel(typename Route::View gv, DecodeArgs a, LayeredLayout lay, Arith ar, Rm... rm) {
@@ -544,14 +611,20 @@ __global__ void __launch_bounds__(kLayeredMaxThreads)
   Route route;
   route.init(gv, smem, lay);
   const int NL = route.layers();
+  constexpr bool kRm = kHasRm<Rm...>, kCrc = kHasCrc<Rm...>;
+  // the CRC bytes of waves this workgroup does not have stay zero; the first
+  // frame's load ends with a barrier
+  if constexpr (kCrc)
+    if (threadIdx.x < kWgRedCrcWords) red[kWgRedCrc + threadIdx.x] = 0;
 
   int64_t b = blockIdx.x;
   while (b < a.B) {
-    if constexpr (sizeof...(Rm) == 0)
-      load_frame(ar, a, b, gv.N, gv.E, lay, LQ, R);
+    if constexpr (kRm)
+      load_frame_rm(ar, a, rm_of(rm...), b, gv.N, gv.E, lay, LQ, R);
     else
-      load_frame_rm(ar, a, rm..., b, gv.N, gv.E, lay, LQ, R);
+      load_frame(ar, a, b, gv.N, gv.E, lay, LQ, R);
     int used = 0, weight = 0;
+    [[maybe_unused]] uint32_t rem = 0;
     for (int h = 0;; ++h) {
       route.rewind();
       for (int l = 0; l < NL; ++l) {
@@ -562,10 +635,20 @@ __global__ void __launch_bounds__(kLayeredMaxThreads)
       // the cap first, then the syndrome on multiples of et_period (:406-408)
       const bool last = used == a.max_iters;
       if (last || used % a.et_period == 0) {
-        weight = route.template syndrome<Arith>(LQ, red);
-        if (last || weight == 0) break;
+        if constexpr (kCrc) {
+          // the remainder of the same decisions, through the syndrome's barrier
+          crc_wave_share<Arith>(crc_of(rm...), LQ, red);
+          weight = route.template syndrome<Arith>(LQ, red);
+          rem = crc_remainder(red);
+          if (last || weight == 0 || (crc_of(rm...).stop && rem == 0)) break;
+        } else {
+          weight = route.template syndrome<Arith>(LQ, red);
+          if (last || weight == 0) break;
+        }
       }
     }
+    if constexpr (kCrc)
+      if (threadIdx.x == 0) crc_of(rm...).out[b] = rem;
     store_frame<Arith>(a, b, gv.M, gv.N, gv.KB, used, weight, LQ, hard);
     b = wg_next_frame(a, b, red);
   }
@@ -601,10 +684,13 @@ int launch_arith(const typename Route::View &g, const DecodeArgs &args, const La
 template <typename Route>
 int launch_route(const typename Route::View &g, const DecodeArgs &args, const LayeredLayout &lay,
                  const LayeredArith &ar, void *stream, int *resident, uint32_t *advance_out,
-                 const RmArgs *rm) {
+                 const RmArgs *rm, const CrcArgs *crc) {
   *advance_out = 0;
   if (args.B <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
+  if (crc)
+    return rm ? launch_arith<Route>(g, args, lay, ar, st, resident, advance_out, *rm, *crc)
+              : launch_arith<Route>(g, args, lay, ar, st, resident, advance_out, *crc);
   return rm ? launch_arith<Route>(g, args, lay, ar, st, resident, advance_out, *rm)
             : launch_arith<Route>(g, args, lay, ar, st, resident, advance_out);
 }
@@ -613,16 +699,17 @@ int launch_route(const typename Route::View &g, const DecodeArgs &args, const La
 
 int launch_layered_decode(const LayeredView &g, const DecodeArgs &args, const LayeredLayout &lay,
                           const LayeredArith &ar, void *stream, int *resident,
-                          uint32_t *advance_out, const RmArgs *rm) {
-  return lay.staged
-             ? launch_route<TableRoute<true>>(g, args, lay, ar, stream, resident, advance_out, rm)
-             : launch_route<TableRoute<false>>(g, args, lay, ar, stream, resident, advance_out, rm);
+                          uint32_t *advance_out, const RmArgs *rm, const CrcArgs *crc) {
+  return lay.staged ? launch_route<TableRoute<true>>(g, args, lay, ar, stream, resident,
+                                                     advance_out, rm, crc)
+                    : launch_route<TableRoute<false>>(g, args, lay, ar, stream, resident,
+                                                      advance_out, rm, crc);
 }
 
 int launch_layered_decode(const LayeredQcView &g, const DecodeArgs &args, const LayeredLayout &lay,
                           const LayeredArith &ar, void *stream, int *resident,
-                          uint32_t *advance_out, const RmArgs *rm) {
-  return launch_route<CirculantRoute>(g, args, lay, ar, stream, resident, advance_out, rm);
+                          uint32_t *advance_out, const RmArgs *rm, const CrcArgs *crc) {
+  return launch_route<CirculantRoute>(g, args, lay, ar, stream, resident, advance_out, rm, crc);
 }
 
 }  // namespace ldpc

@@ -9,6 +9,7 @@
 
 #include <stdint.h>
 
+#include "ldpc_crc.hpp"
 #include "ldpc_kernels.hpp"
 #include "ldpc_layers.hpp"
 #include "ldpc_rate_match.hpp"
@@ -53,15 +54,19 @@ struct LayeredArith {
 // launch error.  rm: the frames are rate-matched samples (ldpc_rate_match.hpp)
 // and the frame load recovers them -- args.cw_stride is the frames' stride,
 // args.elem_stride 1; a kernel of its own, so `resident` is that kernel's.
+// crc: the block's remainder (ldpc_crc.hpp) is evaluated wherever the syndrome
+// is and stored at crc->out[frame]; again kernels of their own.
 int launch_layered_decode(const LayeredView &g, const DecodeArgs &args, const LayeredLayout &lay,
                           const LayeredArith &ar, void *stream, int *resident,
-                          uint32_t *advance_out, const RmArgs *rm = nullptr);
+                          uint32_t *advance_out, const RmArgs *rm = nullptr,
+                          const CrcArgs *crc = nullptr);
 
 // The same for a quasi-cyclic code decoded by its block rows: `lay` is the
 // layout for mb layers of Z rows with nothing staged (lay.total == lay.frame:
 // the base tables are read through the scalar cache).
 int launch_layered_decode(const LayeredQcView &g, const DecodeArgs &args, const LayeredLayout &lay,
                           const LayeredArith &ar, void *stream, int *resident,
-                          uint32_t *advance_out, const RmArgs *rm = nullptr);
+                          uint32_t *advance_out, const RmArgs *rm = nullptr,
+                          const CrcArgs *crc = nullptr);
 
 }  // namespace ldpc

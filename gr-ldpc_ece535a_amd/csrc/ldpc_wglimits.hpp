@@ -18,8 +18,14 @@ constexpr int kWgIndexMax = 65535;       // M, N, E: the tables' 16-bit fields
 // The `red` region every frame layout ends with, in 32-bit words:
 //   [0, 16)  per-wave counts (wg_sum_waves), one word per wave of the workgroup
 //   [16]     the workgroup's next frame (wg_next_frame)
-//   (16, 32) unused
+//   [17, 29) the code-block CRC's per-wave remainders, three bytes per wave
+//            (ldpc_layered.hip crc_wave_share: sixteen 24-bit values do not
+//            fit fifteen words one apiece)
+//   [29, 32) unused
 constexpr int kWgRedWaves = 16, kWgRedNext = 16, kWgRedWords = 32;
+constexpr int kWgRedCrc = 17, kWgRedCrcWords = 12;
+static_assert(kWgRedWaves * 3 == kWgRedCrcWords * 4 && kWgRedCrc + kWgRedCrcWords <= kWgRedWords,
+              "three bytes per wave of the largest workgroup");
 constexpr int kWgRedBytes = kWgRedWords * 4;
 static_assert(kWgMaxThreads / 64 <= kWgRedWaves, "a count word per wave of the largest workgroup");
 

@@ -15,6 +15,7 @@ from ._capi import (  # noqa: F401
     PREC_F32, PREC_F64, PREC_F64_FAST, PREC_F64_LIBM, Decoder, LdpcError, bpsk_awgn, check_frame, count_bit_errors,
     default_h, encode, encode_qc, plan_layers, plan_layers_q8, plan_layout, plan_qc, plan_qc_encoder, plan_qc_q8,
     plan_rate_match, random_bits, rate_match, rate_recover, reorder_h,
+    CRC6, CRC11, CRC16, CRC24A, CRC24B, CRC24C, CRCS, crc_attach, crc_bits, plan_crc,
 )
 from .blocks import (  # noqa: F401,E402
     STATE_IN_SYNC, STATE_IN_SYNC_INVERTED, STATE_OUT_OF_SYNC, ldpc_decoder_cb, ldpc_encoder_bc,

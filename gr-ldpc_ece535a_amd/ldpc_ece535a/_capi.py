@@ -33,6 +33,7 @@ _u8p = ctypes.POINTER(ctypes.c_uint8)
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _f32p = ctypes.POINTER(ctypes.c_float)
 _i64p = ctypes.POINTER(ctypes.c_int64)
+_u32p = ctypes.POINTER(ctypes.c_uint32)
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
 _vp = ctypes.c_void_p
@@ -124,10 +125,25 @@ SIGNATURES = {
     "ldpc_decode_layered_q8_rm_device": (_i, [_vp, _i, ctypes.c_float, _i, _i, _vp, _i64,
                                               ctypes.c_float, _i, _i32p, _i32p, ctypes.c_float, _i,
                                               _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldpc_crc_bits": (_i64, [_i, ctypes.c_uint32, _u8p, _i64]),
+    "ldpc_plan_crc": (_i, [_i, _i, _i, _i, ctypes.c_uint32, _u32p]),
+    "ldpc_crc_attach": (_i, [_i, _i, _i, _i, ctypes.c_uint32, _u8p, _i, _u8p]),
+    "ldpc_set_crc": (_i, [_vp, _i, ctypes.c_uint32, _i]),
+    "ldpc_crc_results": (_i, [_vp, _u32p, _i]),
+    "ldpc_crc_results_device": (_vp, [_vp]),
+    "ldpc_crc_attach_device": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "ldpc_crc_check_device": (_i, [_vp, _vp, _i, _vp, _vp]),
 }
 
 RM_MAX_TX = 4
 UNRECEIVED_LCI = 2.0 ** -100   # what a column no sample reaches gets, by default
+
+# the code-block CRCs by name: (len, poly), poly without the leading term
+CRC24A, CRC24B, CRC24C = (24, 0x864CFB), (24, 0x800063), (24, 0xB2B117)
+CRC16, CRC11, CRC6 = (16, 0x1021), (11, 0x621), (6, 0x21)
+CRCS = {"CRC24A": CRC24A, "CRC24B": CRC24B, "CRC24C": CRC24C, "CRC16": CRC16, "CRC11": CRC11,
+        "CRC6": CRC6}
+CRC_REPORT, CRC_STOP = 0, 1
 
 _lib = None
 
@@ -424,6 +440,36 @@ def rate_recover(M, N, punct, filler, ncb, tx, rx, polarity=1.0, unreceived_lci=
     return out
 
 
+def crc_bits(len, poly, bits):
+    """ldpc_crc_bits (host only, no GPU): the CRC register (start 0, MSB
+    first, no reflection, no final xor) over a 1-D array of bits."""
+    b = np.ascontiguousarray(bits, np.uint8).reshape(-1)
+    return int(_check(lib().ldpc_crc_bits(int(len), int(poly), _p(b, _u8p), b.size)))
+
+
+def plan_crc(M, N, filler, len, poly):
+    """ldpc_plan_crc (host only, no GPU): checks the CRC on an M x N code whose
+    pattern has `filler` fillers.  Returns {A, weights}: the block is the first
+    A = K - filler information bits, weights[p] = x^(A-1-p) mod g."""
+    A = _check(lib().ldpc_plan_crc(int(M), int(N), int(filler), int(len), int(poly), None))
+    w = np.zeros(A, np.uint32)
+    _check(lib().ldpc_plan_crc(int(M), int(N), int(filler), int(len), int(poly), _p(w, _u32p)))
+    return dict(A=A, weights=w)
+
+
+def crc_attach(M, N, filler, len, poly, payload):
+    """ldpc_crc_attach (host only, no GPU): payload (B, A - len) bits -> (B, K)
+    information bits: the payload, its CRC MSB first, `filler` zeros."""
+    A = _check(lib().ldpc_plan_crc(int(M), int(N), int(filler), int(len), int(poly), None))
+    p = np.ascontiguousarray(payload, np.uint8)
+    if p.ndim != 2 or p.shape[1] != A - int(len):
+        raise LdpcError("LDPC_EINVAL: payload must be (B, A - len) = (B, %d)" % (A - int(len)))
+    out = np.zeros((p.shape[0], int(N) - int(M)), np.uint8)
+    _check(lib().ldpc_crc_attach(int(M), int(N), int(filler), int(len), int(poly), _p(p, _u8p),
+                                 p.shape[0], _p(out, _u8p)))
+    return out
+
+
 class Decoder:
     """One decode context (device tables + stream) for one H.
 
@@ -711,7 +757,7 @@ class Decoder:
                                          int(elem_stride), float(polarity), int(B),
                                          _p(packed, _u8p), _p(bits, _u8p), _p(iters, _i32p),
                                          _p(synd, _i32p), _p(post, _f32p)), self._ctx)
-        out = dict(packed=packed, iters=iters, synd=synd)
+        out = self._with_crc(dict(packed=packed, iters=iters, synd=synd), B)
         if want_bits:
             out["bits"] = bits
         if want_llr:
@@ -753,7 +799,7 @@ class Decoder:
                                             int(elem_stride), float(polarity), int(B),
                                             _p(packed, _u8p), _p(bits, _u8p), _p(iters, _i32p),
                                             _p(synd, _i32p), _p(post, _f32p)), self._ctx)
-        out = dict(packed=packed, iters=iters, synd=synd)
+        out = self._with_crc(dict(packed=packed, iters=iters, synd=synd), B)
         if want_bits:
             out["bits"] = bits
         if want_llr:
@@ -772,6 +818,53 @@ class Decoder:
                                                    int(cw_stride), int(elem_stride),
                                                    float(polarity), int(B), d_packed, d_bits,
                                                    d_iters, d_synd, d_llr, stream), self._ctx)
+
+    def set_crc(self, len=0, poly=0, mode="report"):
+        """ldpc_set_crc: the code-block CRC (len, poly) -- e.g. *CRC16 -- that
+        every layered decode of this context checks: the block is the first
+        A = K - filler information bits, payload then CRC.  mode "report": the
+        decode is the plain decode and the remainders are one more output;
+        "stop": a zero remainder also ends a frame, wherever the syndrome is
+        evaluated.  The host decodes then return them as "crc" (0 = pass);
+        crc_results() reads those of a device decode.  len = 0 or mode None
+        turns the CRC off (the default)."""
+        if mode is None or int(len) == 0:
+            len, poly, m = 0, 0, CRC_REPORT
+        elif mode in ("report", "stop"):
+            m = CRC_STOP if mode == "stop" else CRC_REPORT
+        else:
+            raise LdpcError("LDPC_EINVAL: mode must be 'report', 'stop' or None (got %r)" % (mode,))
+        _check(lib().ldpc_set_crc(self._ctx, int(len), int(poly), m), self._ctx)
+        self._crc = (int(len), int(poly)) if int(len) else None
+
+    def crc_results(self, n):
+        """ldpc_crc_results: the remainders of the first n frames of the last
+        layered decode (uint32, 0 = pass), once that decode has finished."""
+        out = np.zeros(int(n), np.uint32)
+        _check(lib().ldpc_crc_results(self._ctx, _p(out, _u32p), int(n)), self._ctx)
+        return out
+
+    def crc_results_device(self):
+        """ldpc_crc_results_device: the device address of the remainders of the
+        last layered decode (None before one), valid until the next decode."""
+        return lib().ldpc_crc_results_device(self._ctx)
+
+    def _with_crc(self, out, B):
+        if getattr(self, "_crc", None):
+            out["crc"] = self.crc_results(B)
+        return out
+
+    def crc_attach_device(self, d_payload, B, d_info, stream=None):
+        """ldpc_crc_attach_device: (B, A - len) payload bytes on the device ->
+        (B, K) information bits (payload, CRC, zero fillers), what
+        encode_device takes."""
+        _check(lib().ldpc_crc_attach_device(self._ctx, d_payload, int(B), d_info, stream),
+               self._ctx)
+
+    def crc_check_device(self, d_packed, B, d_rem, stream=None):
+        """ldpc_crc_check_device: the remainders (uint32, 0 = pass) of (B, KB)
+        packed information bits on the device, as any decode stores them."""
+        _check(lib().ldpc_crc_check_device(self._ctx, d_packed, int(B), d_rem, stream), self._ctx)
 
     def set_rate_match(self, punct=0, filler=0, ncb=0):
         """ldpc_set_rate_match: the context's rate-matching pattern
@@ -820,7 +913,7 @@ class Decoder:
                   len(k0), k0, e, float(unreceived_lci), int(B),
                   _p(packed, _u8p), _p(bits, _u8p), _p(iters, _i32p), _p(synd, _i32p),
                   _p(post, _f32p)), self._ctx)
-        out = dict(packed=packed, iters=iters, synd=synd)
+        out = self._with_crc(dict(packed=packed, iters=iters, synd=synd), B)
         if want_bits:
             out["bits"] = bits
         if want_llr:

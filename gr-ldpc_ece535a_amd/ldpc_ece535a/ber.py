@@ -24,6 +24,7 @@ private copies.
                                [--layered SCALE] [--layered-q8 NUM[:LLR_SCALE]]
                                [--rate-match PUNCT,FILLER,NCB --tx K0:E[,K0:E...]
                                 [--unreceived-lci LCI]]
+                               [--crc NAME[:stop]]
 
 --qc sweeps a quasi-cyclic code in place of --code: codes.qc_parity_core (a
 dual-diagonal core of MC block rows and ME extension rows, the 802.11n /
@@ -53,6 +54,17 @@ convention: sqrt(N0) from Eb/N0 alone, with no code-rate term, so a point of a
 rate-matched sweep is not the Eb/N0 of the code as sent.  The JSON says both.
 --unreceived-lci is what a column no sample reaches enters the decoders with
 (default 2^-100, the binding's).
+
+--crc NAME[:stop] (CRC24A, CRC24B, CRC24C, CRC16, CRC11, CRC6) puts a code-block
+CRC behind random payloads before the encoder (ldpc_crc_attach_device: the
+block is the information bits in front of the fillers) and sets it on the
+context (ldpc_set_crc), so the layered curves check it where they evaluate the
+syndrome -- with ":stop" they also leave on a zero remainder -- and the other
+decoders' packed outputs go through ldpc_crc_check_device.  Per Eb/N0 every
+curve then also reports the frames that passed, the undetected errors among
+them (a pass with a wrong payload) and the mean iterations, in a table of
+comment lines behind the Octave script and in the JSON ("crc_pass",
+"crc_undetected", "iters").
 """
 import argparse
 import json
@@ -81,13 +93,15 @@ RATE_MATCH_NOTE = ("BER over all N codeword bits, the unsent ones included; sigm
 
 def sweep(dec=None, ebn0=DEFAULT_EBN0, frames=30, iterations=5, seed=0, precision=0, device=0,
           layered_scale=None, layered_q8=None, rate_match=None, tx=None,
-          unreceived_lci=_capi.UNRECEIVED_LCI):
+          unreceived_lci=_capi.UNRECEIVED_LCI, crc=None):
     """Returns {method name: {"ber": [...], "fer": [...]}} over `ebn0`; with
     layered_scale also LAYERED, the layered min-sum decoder at that scale; with
     layered_q8 = (num, llr_scale) also LAYERED_Q8, the fixed-point one.  With
     rate_match = (punct, filler, ncb) and tx = [(k0, E), ...] the frames are sent
     rate-matched (see the module's docstring), a column no sample reaches
-    entering every decoder with unreceived_lci."""
+    entering every decoder with unreceived_lci.  With crc = (len, poly, stop)
+    the payloads carry that CRC and every curve also has "crc_pass",
+    "crc_undetected" and "iters" (see the module's docstring)."""
     import torch
     if dec is None:
         dec = _capi.Decoder(device=device)
@@ -109,15 +123,29 @@ def sweep(dec=None, ebn0=DEFAULT_EBN0, frames=30, iterations=5, seed=0, precisio
         filler, total = int(rate_match[1]), sum(int(e) for _, e in tx)
         d_sent = torch.empty((B, total), dtype=torch.uint8, device=dev)
         d_rx = torch.empty((B, total), dtype=torch.float32, device=dev)
+    filler = int(rate_match[1]) if rate_match is not None else 0
+    if crc is not None:
+        dec.set_crc(crc[0], crc[1], mode="stop" if crc[2] else "report")
+        P = K - filler - crc[0]
+        d_payload = torch.empty((B, P), dtype=torch.uint8, device=dev)
+        d_rem = torch.empty(B, dtype=torch.int32, device=dev)
+        d_iters = torch.empty(B, dtype=torch.int32, device=dev)
     runs = (list(METHODS) + ([(LAYERED, None)] if layered_scale is not None else []) +
             ([(LAYERED_Q8, None)] if layered_q8 is not None else []))
     out = {name: {"ber": [], "fer": []} for name, _ in runs}
+    if crc is not None:
+        for r in out.values():
+            r.update(crc_pass=[], crc_undetected=[], iters=[])
     for i, db in enumerate(ebn0):
         s0 = (int(seed) * 1000003 + i) & 0xFFFFFFFF
-        _capi.random_bits(d_data.data_ptr(), B * K, s0, sp)
-        if rate_match is not None and filler:
-            with torch.cuda.stream(stream):
-                d_data[:, K - filler:] = 0
+        if crc is not None:
+            _capi.random_bits(d_payload.data_ptr(), B * P, s0, sp)
+            dec.crc_attach_device(d_payload.data_ptr(), B, d_data.data_ptr(), sp)
+        else:
+            _capi.random_bits(d_data.data_ptr(), B * K, s0, sp)
+            if filler:
+                with torch.cuda.stream(stream):
+                    d_data[:, K - filler:] = 0
         dec.encode_device(d_data.data_ptr(), B, d_cw.data_ptr(), sp)
         if rate_match is None:
             _capi.bpsk_awgn(d_cw.data_ptr(), B * N, sigma_of(db), s0 ^ 0x5DEECE66D,
@@ -137,6 +165,10 @@ def sweep(dec=None, ebn0=DEFAULT_EBN0, frames=30, iterations=5, seed=0, precisio
         for name, m in runs:
             kw = dict(max_iters=iterations, precision=precision, d_bits=d_bits.data_ptr(),
                       d_synd=d_synd.data_ptr(), stream=sp)
+            if crc is not None:
+                kw["d_iters"] = d_iters.data_ptr()
+                with torch.cuda.stream(stream):
+                    d_iters.zero_()     # a decoder without iterations leaves it
             if rate_match is not None and name == LAYERED_Q8:
                 del kw["precision"]
                 dec.decode_layered_q8_rm_device(d_rx.data_ptr(), B, tx, d_packed.data_ptr(),
@@ -161,6 +193,20 @@ def sweep(dec=None, ebn0=DEFAULT_EBN0, frames=30, iterations=5, seed=0, precisio
             synd = d_synd.cpu().numpy()
             out[name]["ber"].append(float((err / N).mean()) if B else 0.0)
             out[name]["fer"].append(int((synd > 0).sum()))
+            if crc is not None:
+                if m is None:   # the layered decodes filled the context's array
+                    rem = dec.crc_results(B)
+                else:
+                    dec.crc_check_device(d_packed.data_ptr(), B, d_rem.data_ptr(), sp)
+                    stream.synchronize()
+                    rem = d_rem.cpu().numpy().view(np.uint32)
+                with torch.cuda.stream(stream):
+                    wrong = (d_bits[:, N - K:N - K + P] != d_payload).any(dim=1)
+                stream.synchronize()
+                ok = rem == 0
+                out[name]["crc_pass"].append(int(ok.sum()))
+                out[name]["crc_undetected"].append(int((ok & wrong.cpu().numpy()).sum()))
+                out[name]["iters"].append(float(d_iters.cpu().numpy().mean()) if B else 0.0)
     return out
 
 
@@ -211,6 +257,19 @@ def octave(ebn0, res):
     return "\n".join(lines) + "\n"
 
 
+def crc_table(ebn0, res):
+    """The CRC figures as Octave comment lines: per curve and Eb/N0 the frames
+    that passed, the undetected errors among them, the mean iterations."""
+    lines = ["% CRC: frames passed / undetected errors / mean iterations"]
+    for name, r in res.items():
+        if "crc_pass" not in r:
+            continue
+        lines.append("% " + name)
+        for db, p, u, it in zip(ebn0, r["crc_pass"], r["crc_undetected"], r["iters"]):
+            lines.append("%%   %6.2f dB  %6d %6d %8.2f" % (db, p, u, it))
+    return "\n".join(lines) + "\n"
+
+
 def parse_range(text):
     """'a:b:step' (inclusive) or a comma list."""
     if ":" in text:
@@ -249,7 +308,17 @@ def main(argv=None):
                     help="with --rate-match: the Lci of a column no sample reaches (default "
                          "2^-100; 2^-10 keeps the float decoders' later iterations alive, see "
                          "DESIGN section 7f)")
+    ap.add_argument("--crc", default=None, metavar="NAME[:stop]",
+                    help="attach this code-block CRC (%s) to random payloads and check it in "
+                         "every decode; ':stop': the layered decoders also leave on a zero "
+                         "remainder" % ", ".join(sorted(_capi.CRCS)))
     a = ap.parse_args(argv)
+    crc = None
+    if a.crc is not None:
+        cname, _, cmode = a.crc.partition(":")
+        if cname not in _capi.CRCS or cmode not in ("", "stop"):
+            ap.error("--crc takes NAME[:stop], NAME one of " + ", ".join(sorted(_capi.CRCS)))
+        crc = _capi.CRCS[cname] + (cmode == "stop",)
     rate_match = tx = None
     if (a.rate_match is None) != (a.tx is None):
         ap.error("--rate-match and --tx go together")
@@ -282,8 +351,11 @@ def main(argv=None):
         dec = _capi.Decoder()
     grid = parse_range(a.ebn0)
     res = sweep(dec, grid, a.frames, a.iterations, a.seed, a.precision, layered_scale=a.layered,
-                layered_q8=q8, rate_match=rate_match, tx=tx, unreceived_lci=a.unreceived_lci)
+                layered_q8=q8, rate_match=rate_match, tx=tx, unreceived_lci=a.unreceived_lci,
+                crc=crc)
     sys.stdout.write(octave(grid, res))
+    if crc is not None:
+        sys.stdout.write(crc_table(grid, res))
     if a.json:
         doc = {"ebn0": grid, "frames": a.frames, "iterations": a.iterations, "code": code,
                "results": res}
@@ -292,6 +364,9 @@ def main(argv=None):
                                  "ncb": rate_match[2], "tx": [list(t) for t in tx],
                                  "unreceived_lci": a.unreceived_lci,
                                  "note": RATE_MATCH_NOTE}
+        if crc is not None:
+            doc["crc"] = {"name": a.crc.partition(":")[0], "len": crc[0], "poly": crc[1],
+                          "mode": "stop" if crc[2] else "report"}
         json.dump(doc, open(a.json, "w"), indent=1)
     return 0
 

@@ -675,6 +675,95 @@ int ldpc_decode_layered_q8_rm_device(ldpc_ctx *ctx, int num, float llr_scale, in
                                      int32_t *d_iters_used_opt, int32_t *d_syn_weight_opt,
                                      float *d_llr_out_opt, void *hip_stream);
 
+/* The code-block CRC: attached in front of the encoder, and checked by the
+ * layered decodes where they evaluate the syndrome -- a per-frame pass/fail
+ * flag, and in LDPC_CRC_STOP mode an earlier exit (the information bits settle
+ * before the parity bits do).
+ *
+ * The polynomial.  A CRC is (len, poly), 1 <= len <= 24; poly is the generator
+ * g without its leading term, poly < 2^len.  The register starts at 0, bits
+ * enter MSB first, nothing is reflected and there is no final xor (the 3GPP
+ * convention): over bits b_0 .. b_{n-1} the register ends as
+ *   (b_0 x^(n-1) + ... + b_{n-1}) x^len  mod g.
+ * Over the 72 bits of ASCII "123456789", MSB first: CRC16 0x31C3, CRC24A
+ * 0xCDE703, CRC24B 0x23EF52, CRC24C 0xF48279, CRC11 0x5CA, CRC6 0x15.
+ *
+ * Where it sits.  K = N - M; information bit p is column M + p (rate
+ * matching's transmit order); `filler` is the context's rate-matching filler
+ * count (0 while no pattern is set).  The block is the A = K - filler
+ * positions [0, A): the payload in [0, A - len), the payload's register in
+ * [A - len, A), MSB first.  The fillers behind it are no part of it.  A > len
+ * is required: ldpc_set_crc, ldpc_plan_crc and ldpc_crc_attach return
+ * LDPC_EINVAL with the values in the message otherwise, and so does
+ * ldpc_set_rate_match while a CRC is set that its fillers would leave no
+ * payload.
+ *
+ * The remainder of a frame is its A decided block bits, taken as a polynomial
+ * (position p has degree A - 1 - p), modulo g: a uint32_t, 0 means pass.  It is
+ * the XOR of w[p] = x^(A-1-p) mod g over the positions that decided 1, and
+ * equals register(payload bits) ^ the CRC field read MSB first.  An attached
+ * block has remainder 0, every single-bit error a non-zero one, and the
+ * all-zero block passes.
+ *
+ * ldpc_set_crc(ctx, len, poly, mode).  len = 0 turns the CRC off: the default,
+ * and then every decode is what it was.  While a CRC is set, every layered
+ * decode of the context (float and q8, plain and _rm, host and device, every
+ * route; the signatures are unchanged) also fills the context's array of
+ * remainders, frame b in word b:
+ *   LDPC_CRC_REPORT  the decode is the plain decode -- bits, packed, iters,
+ *                    synd and llr are bit for bit the same -- and the
+ *                    remainder is that of the stored decisions.
+ *   LDPC_CRC_STOP    wherever the loop evaluates the syndrome (the cap and the
+ *                    multiples of et_period) it evaluates the remainder of
+ *                    the same decisions, and leaves on
+ *                    last || weight == 0 || remainder == 0.  synd is the
+ *                    weight at that point and may be non-zero; the remainder
+ *                    stored is the one at that point.
+ * The check costs a frame no LDS: the planners' answers do not change.
+ *
+ *   ldpc_crc_bits          (no GPU) the register over bit 0 of n bytes, or
+ *                          LDPC_EINVAL.
+ *   ldpc_plan_crc          (no GPU) checks a CRC on an M x N code with
+ *                          `filler` fillers; weights_out_opt[A] receives w.
+ *                          Returns A, or LDPC_EINVAL.
+ *   ldpc_crc_attach        (no GPU) payload (B, A - len) bytes -> info_out
+ *                          (B, K) bytes: payload, CRC, zero fillers.
+ *   ldpc_crc_results       copies the first n <= B remainders of the last
+ *                          layered decode to the host, behind that decode on
+ *                          its stream (synchronous).
+ *   ldpc_crc_results_device  the device array itself (NULL before the first
+ *                          decode): valid until the context's next decode.
+ *   ldpc_crc_attach_device ldpc_crc_attach with the context's CRC and fillers
+ *                          on device buffers: what ldpc_encode_device takes.
+ *   ldpc_crc_check_device  the remainders of (B, KB) packed information bits,
+ *                          as every decode of this library stores them: gives
+ *                          the flooding, on-chip and ring decodes the check. */
+#define LDPC_CRC_REPORT 0
+#define LDPC_CRC_STOP 1
+#define LDPC_CRC24A_LEN 24
+#define LDPC_CRC24A_POLY 0x864CFBu
+#define LDPC_CRC24B_LEN 24
+#define LDPC_CRC24B_POLY 0x800063u
+#define LDPC_CRC24C_LEN 24
+#define LDPC_CRC24C_POLY 0xB2B117u
+#define LDPC_CRC16_LEN 16
+#define LDPC_CRC16_POLY 0x1021u
+#define LDPC_CRC11_LEN 11
+#define LDPC_CRC11_POLY 0x621u
+#define LDPC_CRC6_LEN 6
+#define LDPC_CRC6_POLY 0x21u
+int64_t ldpc_crc_bits(int len, uint32_t poly, const uint8_t *bits, int64_t n);
+int ldpc_plan_crc(int M, int N, int filler, int len, uint32_t poly, uint32_t *weights_out_opt);
+int ldpc_crc_attach(int M, int N, int filler, int len, uint32_t poly, const uint8_t *payload,
+                    int B, uint8_t *info_out);
+int ldpc_set_crc(ldpc_ctx *ctx, int len, uint32_t poly, int mode);
+int ldpc_crc_results(ldpc_ctx *ctx, uint32_t *out, int n);
+const uint32_t *ldpc_crc_results_device(const ldpc_ctx *ctx);
+int ldpc_crc_attach_device(ldpc_ctx *ctx, const uint8_t *d_payload, int B, uint8_t *d_info_out,
+                           void *hip_stream);
+int ldpc_crc_check_device(ldpc_ctx *ctx, const uint8_t *d_packed, int B, uint32_t *d_rem_out,
+                          void *hip_stream);
+
 /* The frame ring: ONE persistent launch decodes every batch posted to it
  * (small codes; min-sum and sum-product, any precision).  The frames of all
  * posted batches form one device queue, so a wave that finishes a frame of
