@@ -25,9 +25,16 @@ namespace ldpc {
 //               it is the reference's arithmetic in float and is held bit for
 //               bit to the oracle's float restatement
 //               (tests/test_gpu_minsum_f32.py).  Sum-product uses ROCm's
-//               tanhf / logf and, like mode 3 (whose compact forms start from
-//               the device's reciprocal seed), has no oracle: neither can be
-//               restated bit for bit on a host
+//               tanhf / logf.  Neither they nor mode 3's compact forms (which
+//               start from the device's reciprocal seed) can be restated on a
+//               host, so the device evaluates them for the tests
+//               (ldpc_probe.hip): the functions are held operand by operand
+//               (tests/test_gpu_math.py: modes 0 / 2 to glibc's bits, mode 3 to
+//               the bounds above, f32 to the host's tanhf / logf + 1 ulp), and
+//               the decodes to a numpy restatement around those two functions
+//               (tests/test_gpu_sumproduct_inexact.py), bit for bit on every
+//               route of scalar Math calls; mode 3's small-code route, which
+//               picks batched forms per frame, to an enclosure
 // tanh_half(m) = tanh(m / 2) (:509); check_msg(T, tab) = log((1+T)/(1-T))
 // (:513); the _n forms take n independent operands (a lane's edge slots /
 // column entries) so their divisions can share one reciprocal.  `Tab` is

@@ -580,17 +580,54 @@ LDPC_HD double log_ratio_fast(double T) {
 // product can reach 1.
 LDPC_HD double log_ratio_tab_open(double T, const LogTabEntry *tab);
 
+#if defined(__HIP_DEVICE_COMPILE__)
+// wave-uniform "does any lane need this", and the first statement of such a
+// rare region (ldpc_exact.hpp's LDPC_EX_ANY / LDPC_EX_COLD)
+#define LDPC_FM_ANY(c) (__builtin_amdgcn_ballot_w64(c) != 0)
+#define LDPC_FM_COLD() asm volatile(";ldpc_cold")
+#else
+#define LDPC_FM_ANY(c) (c)
+#define LDPC_FM_COLD() ((void)0)
+#endif
+
+// A T whose ratio the table logs must take from an IEEE division.  div_fast's
+// quotient is the correctly rounded one unless the exact quotient lies within
+// about 2^-48 ulp of a rounding boundary (the refined reciprocal carries the
+// seed's squared error: v_rcp_f64 is off by up to 2^-24).  Generic operands are
+// never that close.  But for |T| < 2^-49, 1 + T and 1 - T are 1 plus a few units
+// of 2^-53, and their quotient 1 + (2a + b) 2^-53 + (2a + b) b 2^-106 lies a few
+// 2^-54 ulp from a midpoint whenever b is odd: the device then returns the
+// other neighbour, and since log(q) next to 1 is q - 1 itself, one ulp of q is
+// tens of per cent of the result (tests/test_gpu_math.py found 4.44e-16 for
+// glibc's 6.66e-16 at T = 3.33e-16; the host's exact 1.0 / d hides it).  The
+// bound 2^-40 leaves a wide margin.  T = +-0 (every padding cell) gives q = 1
+// either way and is left out, so a wave takes the branch only for a real edge
+// with a vanishing product.
+LDPC_HD bool ratio_needs_ieee(double T) { return T != 0.0 && __builtin_fabs(T) < 0x1p-40; }
+
+// (1 + T) / (1 - T) for the table logs: div_fast, and the IEEE quotient where
+// a lane of the wave holds a ratio_needs_ieee T.
+LDPC_HD double ratio_fast(double T) {
+  double q = div_fast(1.0 + T, 1.0 - T);
+  const bool tiny = ratio_needs_ieee(T);
+  if (LDPC_FM_ANY(tiny)) {
+    LDPC_FM_COLD();
+    q = tiny ? (1.0 + T) / (1.0 - T) : q;
+  }
+  return q;
+}
+
 // log((1+T)/(1-T)) with a table-driven log (tools/gen_logtab.py): the same
 // ratio q as log_ratio_fast, then q = 2^k z, z in [0.6875, 1.375), bucket i
 // from the top 9 bits, r = z invc_i - 1 (|r| < 1/512), log(q) = k ln2 +
 // logc_i + log1p(r) with log1p(r) - r = r^2 (-1/2 + r/3 - ... - r^4/6).  The
 // buckets touching 1.0 use c = 1 (logc = 0, r = z - 1 exact), so results near
-// 0 keep full relative accuracy.  `tab` is the 512-entry table (in LDS on the
+// 0 keep full relative accuracy -- given the IEEE ratio there (ratio_fast).  `tab` is the 512-entry table (in LDS on the
 // GPU).  |T| == 1 -> +-inf, NaN -> NaN.
 LDPC_HD double log_ratio_tab(double T, const LogTabEntry *tab) {
   const double ln2_hi = 6.93147180369123816490e-01;  // 21 trailing zero bits
   const double ln2_lo = 1.90821492927058770002e-10;
-  const double q = div_fast(1.0 + T, 1.0 - T);
+  const double q = ratio_fast(T);
   uint64_t ix;
   __builtin_memcpy(&ix, &q, 8);
   // bucket, exponent and reduced argument from the high word alone (32-bit ops)
@@ -665,7 +702,7 @@ LDPC_HD double log_q_tab_open(double q, const LogTabEntry *tab) {
 }
 
 LDPC_HD double log_ratio_tab_open(double T, const LogTabEntry *tab) {
-  return log_q_tab_open(div_fast(1.0 + T, 1.0 - T), tab);
+  return log_q_tab_open(ratio_fast(T), tab);
 }
 
 // log_ratio_tab_open of n products with one batched division (div_fast_n);
@@ -678,6 +715,12 @@ LDPC_HD void log_ratio_tab_open_n(const double (&T)[n], const LogTabEntry *tab, 
     den[i] = 1.0 - T[i];
   }
   div_fast_n<n>(num, den, q);
+  bool tiny = false;
+  for (int i = 0; i < n; ++i) tiny |= ratio_needs_ieee(T[i]);
+  if (LDPC_FM_ANY(tiny)) {  // ratio_fast's rare branch, once for the n ratios
+    LDPC_FM_COLD();
+    for (int i = 0; i < n; ++i) q[i] = ratio_needs_ieee(T[i]) ? num[i] / den[i] : q[i];
+  }
   for (int i = 0; i < n; ++i) out[i] = log_q_tab_open(q[i], tab);
 }
 

@@ -23,6 +23,10 @@ FLAG_ONCHIP = 8
 FLAG_QC_TABLES = 16
 TEST_SERVE_UNCHECKED, TEST_SERVE_EPOCH, TEST_SERVE_EPOCH_NOW, TEST_STREAM_OVERLAP = 1, 2, 3, 4
 SERVE_EPOCH_LIMIT = (1 << 23) - (1 << 16)
+# ldpc_math_probe's functions (test seam)
+(PROBE_TANH_HALF, PROBE_TANH_HALF_MASKED, PROBE_TANH_HALF_SMALL3, PROBE_CHECK_MSG,
+ PROBE_CHECK_MSG_PACKED, PROBE_CHECK_MSG_PACKED_LEAN, PROBE_CHECK_MSG_OPEN3, PROBE_DIV1,
+ PROBE_DIV2, PROBE_DIV3) = range(10)
 PATH_SMALL, PATH_GRAPH, PATH_ONCHIP = 0, 1, 2
 MODE_LATENCY, MODE_THROUGHPUT = 0, 1
 ERRORS = {0: "LDPC_OK", -1: "LDPC_EINVAL", -2: "LDPC_EUNSUPPORTED", -3: "LDPC_EDEVICE",
@@ -82,6 +86,7 @@ SIGNATURES = {
     "ldpc_set_schedule": (_i, [_vp, _i]),
     "ldpc_synchronize": (_i, [_vp]),
     "ldpc_test_hook": (_i, [_vp, _i, _i64]),
+    "ldpc_math_probe": (_i, [_vp, _i, _i, _vp, _vp, _i64, _vp]),
     "ldpc_ring_begin": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "ldpc_ring_post": (_i64, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "ldpc_ring_wait": (_i, [_vp, _i64]),
@@ -702,6 +707,13 @@ class Decoder:
         """ldpc_test_hook (test seam): TEST_SERVE_UNCHECKED, TEST_SERVE_EPOCH,
         TEST_SERVE_EPOCH_NOW."""
         return _check(lib().ldpc_test_hook(self._ctx, int(op), int(arg)), self._ctx)
+
+    def math_probe(self, fn, precision, d_a, n, d_out, d_b=None):
+        """ldpc_math_probe (test seam): function `fn` (PROBE_*) of the kernels'
+        arithmetic at `precision` on n device reals at d_a (and d_b), to d_out;
+        enqueued on the context's stream."""
+        return _check(lib().ldpc_math_probe(self._ctx, int(fn), int(precision), d_a, d_b, int(n),
+                                            d_out), self._ctx)
 
     def serve_end(self):
         _check(lib().ldpc_serve_end(self._ctx), self._ctx)

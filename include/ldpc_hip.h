@@ -412,6 +412,47 @@ int ldpc_serve_end(ldpc_ctx *ctx);
 #define LDPC_TEST_STREAM_OVERLAP 4
 int ldpc_test_hook(ldpc_ctx *ctx, int op, int64_t arg);
 
+/* Math probe: a test seam (tests/test_gpu_math.py,
+ * tests/test_gpu_sumproduct_inexact.py; not for production callers).
+ * Evaluates one function of the decode kernels' arithmetic elementwise on the
+ * device, through the calls the kernels make, so that each can be held to the
+ * host libm with the device's own reciprocal seed and its wave-uniform cold
+ * branches.  d_a, d_b_opt and d_out are device arrays of n reals of the
+ * precision's type (double for precisions 0, 2 and 3, float for 1); n is a
+ * multiple of 3, and one thread takes one group of three consecutive operands
+ * (the kernels' batches of three), so a wave holds 64 unrelated groups.  It
+ * writes out[0 .. n) and nothing else, on the context's stream, without
+ * synchronising.  d_b_opt is read by TANH_HALF_MASKED and DIV1..3 only.
+ *
+ *   fn                      precisions 0 / 2              3                         1
+ *   TANH_HALF               Math<P>::tanh_half_n<3>       Math<3>::tanh_half        Math<1>::tanh_half
+ *   TANH_HALF_MASKED        (0) the masked overload; lane masked where b != 0: a's
+ *                           operand there must be the +-0 a structural zero holds
+ *   TANH_HALF_SMALL3        -                             fm::tanh_half_small_n<3>  -
+ *   CHECK_MSG               Math<P>::check_msg_n<3>       Math<3>::check_msg, table  Math<1>::check_msg
+ *                                                         staged in LDS
+ *   CHECK_MSG_PACKED[_LEAN] (0) log_ratio_n_packed<3, LEAN> on a per-wave LDS scratch
+ *                           of 64 x 3 doubles and a zero cell
+ *   CHECK_MSG_OPEN3         -                             fm::log_ratio_tab_open_n<3>  -
+ *   DIV1, DIV2, DIV3        ex::div_n<k> of a[i] / b[i]; k < 3: the group's operands  -
+ *                           in batches of k, padded with the pair (1, 1)
+ *                           precision 3, DIV3 only: fm::div_fast_n<3>
+ *
+ * LDPC_EINVAL with a message for an unknown fn or precision, a cell of the table
+ * that does not exist, n < 0 or not a multiple of 3, or a missing array. */
+#define LDPC_PROBE_TANH_HALF 0
+#define LDPC_PROBE_TANH_HALF_MASKED 1
+#define LDPC_PROBE_TANH_HALF_SMALL3 2
+#define LDPC_PROBE_CHECK_MSG 3
+#define LDPC_PROBE_CHECK_MSG_PACKED 4
+#define LDPC_PROBE_CHECK_MSG_PACKED_LEAN 5
+#define LDPC_PROBE_CHECK_MSG_OPEN3 6
+#define LDPC_PROBE_DIV1 7
+#define LDPC_PROBE_DIV2 8
+#define LDPC_PROBE_DIV3 9
+int ldpc_math_probe(ldpc_ctx *ctx, int fn, int precision, const void *d_a, const void *d_b_opt,
+                    int64_t n, void *d_out);
+
 /* Device-resident buffers (already in HBM); enqueues on `hip_stream`
  * (hipStream_t, NULL = the context's own stream) and returns without
  * synchronising -- except min-sum on a large-code context, whose pass loop

@@ -934,3 +934,29 @@ int orc_block_general_work_sparse(orc_block *blk, const int32_t *row_ptr, const 
   orc_graph_free(&g);
   return made;
 }
+
+/* ---- the host libm, elementwise (the expressions of orc_sumproduct_sparse) ---- */
+
+void orc_tanh_half(const double *x, long n, double *out) {
+  for (long i = 0; i < n; i++) out[i] = tanh(x[i] / 2.0);
+}
+
+void orc_log_ratio(const double *T, long n, double *out) {
+  for (long i = 0; i < n; i++) out[i] = log((1.0 + T[i]) / (1.0 - T[i]));
+}
+
+void orc_div(const double *a, const double *b, long n, double *out) {
+  for (long i = 0; i < n; i++) out[i] = a[i] / b[i];
+}
+
+void orc_tanh_half_f32(const float *x, long n, float *out) {
+  for (long i = 0; i < n; i++) out[i] = tanhf(x[i] / 2.0f);
+}
+
+void orc_log_f32(const float *q, long n, float *out) {
+  for (long i = 0; i < n; i++) out[i] = logf(q[i]);
+}
+
+void orc_log_ratio_f32(const float *T, long n, float *out) {
+  for (long i = 0; i < n; i++) out[i] = logf((1.0f + T[i]) / (1.0f - T[i]));
+}

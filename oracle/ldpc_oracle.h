@@ -155,6 +155,19 @@ int orc_block_general_work_sparse(orc_block *blk, const int32_t *row_ptr, const 
                                   int noutput_items, int ninput_items, const float *in_complex,
                                   uint8_t *out, int *consumed);
 
+/* The host libm's values, elementwise: the expressions of the sum-product
+ * restatement above (tanh(Q / 2.0), log((1.0 + T) / (1.0 - T)), IEEE
+ * division), for tests that compare a device function with them operand by
+ * operand or plug them into a numpy restatement (tests/sumproduct_ref.py).
+ * The float forms are the same expressions in float: tanhf(x / 2.0f), logf(q)
+ * of a given q, and logf((1.0f + T) / (1.0f - T)).  out may not alias an input. */
+void orc_tanh_half(const double *x, long n, double *out);
+void orc_log_ratio(const double *T, long n, double *out);
+void orc_div(const double *a, const double *b, long n, double *out);
+void orc_tanh_half_f32(const float *x, long n, float *out);
+void orc_log_f32(const float *q, long n, float *out);
+void orc_log_ratio_f32(const float *T, long n, float *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,11 @@ def lib():
         L.orc_block_general_work_sparse.argtypes = [ctypes.c_void_p, _i32p, _i32p, ctypes.c_int,
                                                     ctypes.c_int, _f32p, _u8p, _i32p]
         L.orc_block_general_work_sparse.restype = ctypes.c_int
+        for name, t, k in (("orc_tanh_half", _f64p, 1), ("orc_log_ratio", _f64p, 1),
+                           ("orc_div", _f64p, 2), ("orc_tanh_half_f32", _f32p, 1),
+                           ("orc_log_f32", _f32p, 1), ("orc_log_ratio_f32", _f32p, 1)):
+            getattr(L, name).argtypes = [t] * k + [ctypes.c_long, t]
+            getattr(L, name).restype = None
         _lib = L
     return _lib
 
@@ -219,6 +224,46 @@ def decode_batch_sparse(method, row_ptr, col_idx, M, N, llr, iterations, polarit
     if f32 and want_post:
         out["post"] = post
     return out
+
+
+def _elementwise(name, dtype, *arrays):
+    t = _f64p if dtype == np.float64 else _f32p
+    arrays = [np.ascontiguousarray(a, dtype) for a in arrays]
+    shape = arrays[0].shape
+    assert all(a.shape == shape for a in arrays)
+    out = np.empty(shape, dtype)
+    getattr(lib(), name)(*[_p(a, t) for a in arrays], int(out.size), _p(out, t))
+    return out
+
+
+def tanh_half(x):
+    """glibc's tanh(x / 2.0), elementwise (float64)."""
+    return _elementwise("orc_tanh_half", np.float64, x)
+
+
+def log_ratio(T):
+    """glibc's log((1.0 + T) / (1.0 - T)), elementwise (float64)."""
+    return _elementwise("orc_log_ratio", np.float64, T)
+
+
+def div(a, b):
+    """a / b in C doubles, elementwise."""
+    return _elementwise("orc_div", np.float64, a, b)
+
+
+def tanh_half_f32(x):
+    """glibc's tanhf(x / 2.0f), elementwise (float32)."""
+    return _elementwise("orc_tanh_half_f32", np.float32, x)
+
+
+def log_f32(q):
+    """glibc's logf(q), elementwise (float32)."""
+    return _elementwise("orc_log_f32", np.float32, q)
+
+
+def log_ratio_f32(T):
+    """glibc's logf((1.0f + T) / (1.0f - T)), elementwise (float32)."""
+    return _elementwise("orc_log_ratio_f32", np.float32, T)
 
 
 def dense_to_csr(H):

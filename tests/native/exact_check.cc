@@ -97,6 +97,13 @@ void check_div(int k, const double *a, const double *b, int64_t n, int64_t *out)
   }
 }
 
+// the host libm's own values, for the tests that hold the oracle's elementwise
+// helpers to them: fn 0 tanh(a / 2.0), 1 log((1.0 + a) / (1.0 - a)), 2 a / b
+void libm_eval(int fn, const double *a, const double *b, int64_t n, double *out) {
+  for (int64_t i = 0; i < n; ++i)
+    out[i] = fn == 0 ? tanh(a[i] / 2.0) : fn == 1 ? log((1.0 + a[i]) / (1.0 - a[i])) : a[i] / b[i];
+}
+
 // the glibc constants this build carries match the libm it runs against:
 // log_glibc vs log on a fixed sweep of every table subinterval and both paths
 int64_t self_check(void) {

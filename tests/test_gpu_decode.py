@@ -53,7 +53,8 @@ def test_default_h_fixtures_f64(dec_by_schedule, golden, db, method, iters, prec
 @pytest.mark.parametrize("db", [0, 2, 4])
 @pytest.mark.parametrize("method", [0, 1])
 def test_default_h_f32_hard_decisions(dec, golden, db, method):
-    """f32: sum-product (ROCm's tanhf / logf, no oracle) gives the f64
+    """f32: sum-product (ROCm's tanhf / logf: no host oracle, see
+    tests/test_gpu_sumproduct_inexact.py for the assembled one) gives the f64
     oracle's hard decisions on these fixtures and posterior LLRs within the
     stated f32 tolerance; min-sum is the reference's arithmetic in float and
     equals the float oracle on every frame, posteriors bit for bit."""

@@ -331,7 +331,9 @@ def test_ring_and_server_are_refused(c720):
 @pytest.mark.parametrize("prec", [1, 3])
 @pytest.mark.parametrize("method", [0, 1])
 def test_inexact_modes_equal_large_code_path(odec, golden, method, prec):
-    """Sum-product at precisions 1 (f32) and 3 (compact f64) has no oracle;
+    """Sum-product at precisions 1 (f32) and 3 (compact f64) has no host
+    oracle (tests/test_gpu_sumproduct_inexact.py holds both paths to one
+    assembled from the device's functions);
     the large-code kernels evaluate the same scalar Math<PREC> calls in the
     same order with contraction off, so every output is equal, posteriors bit
     for bit.  Min-sum has one at either precision: the oracle's float

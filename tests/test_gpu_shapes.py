@@ -310,8 +310,10 @@ def test_window_server_refuses_eight_slots(ctx):
 @cases(SMALL + LARGE)
 def test_fast_modes(ctx, method, prec):
     """Sum-product at precisions 1 (f32: ROCm's tanhf / logf) and 3 (compact
-    f64: the device's reciprocal seed) has no oracle: neither can be restated
-    bit for bit on a host.  Whatever the rounding: the noise-free frame
+    f64: the device's reciprocal seed) has no host oracle: neither can be restated
+    bit for bit on a host (on the default H, tests/test_gpu_sumproduct_inexact.py
+    holds them to an oracle assembled from the device's functions).  On every
+    shape, whatever the rounding: the noise-free frame
     decodes in one iteration to a zero syndrome and the oracle's bits (zero
     on every column that has a check), frames the oracle decodes within 5
     iterations get the oracle's decisions, and the planned and the plain

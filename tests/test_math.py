@@ -9,6 +9,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import math_sets
+from math_sets import SPECIALS, inputs as _inputs
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "native", "math_check.cc")
 
@@ -27,17 +30,6 @@ def _run(mc, fname, fn, x):
     getattr(mc, fname)(fn, x.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(x.size),
                        out.ctypes.data_as(ctypes.c_void_p))
     return out
-
-
-SPECIALS = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 5e-324, -5e-324, 1e-310, 2.0 ** -55,
-                     2.0 ** -54, 22.0, -22.0, 21.999, 1.0, -1.0, 0.34657359, 1.0397, 38.8,
-                     44.0, 1e300, -1e300])
-
-
-def _inputs(seed, n=400_000):
-    rng = np.random.default_rng(seed)
-    return [rng.uniform(-1, 1, n), rng.uniform(-30, 30, n), rng.normal(0, 8, n),
-            rng.uniform(-1, 1, n) * 10.0 ** rng.uniform(-20, 0, n), SPECIALS]
 
 
 def test_tanh_bit_identical_to_libm(mc):
@@ -99,11 +91,7 @@ def test_check_pass_forms(mc):
         assert mism == 0
         _, maxulp = _run(mc, "check_pass", 0, x)
         assert maxulp <= 3
-    rng = np.random.default_rng(14)
-    Ts = [rng.uniform(-1, 1, 400_000), np.tanh(rng.normal(0, 10, 400_000)),
-          1 - 10.0 ** rng.uniform(-16, 0, 200_000), -1 + 10.0 ** rng.uniform(-16, 0, 200_000),
-          np.array([1.0, -1.0, 0.0, -0.0, np.nan, 0.5, -0.5, 1 - 2.0 ** -53, -1 + 2.0 ** -53])]
-    for T in Ts:
+    for T in math_sets.check_pass_ratio_sets():
         _, maxulp = _run(mc, "check_pass", 1, T)
         assert maxulp <= 3
 
@@ -117,12 +105,9 @@ def test_two_range_tanh_matches_libm_near_one(mc):
     within 3 ulp below (the single-range form there).  The
     uncapped single-range form of the fast path equals tanh_half_fast
     wherever it is used (|m| <= 44)."""
-    rng = np.random.default_rng(21)
-    far = np.concatenate([rng.uniform(16, 60, 400_000), -rng.uniform(16, 60, 400_000),
-                          np.array([np.inf, -np.inf, 44.0, 38.0, 100.0, 1e300])])
+    far, mid = math_sets.two_range_sets()
     mism, _ = _run(mc, "check_pass", 3, far)
     assert mism == 0
-    mid = rng.uniform(8, 16, 400_000) * rng.choice([-1.0, 1.0], 400_000)
     mism, maxulp = _run(mc, "check_pass", 3, mid)
     assert mism <= 8 and maxulp <= 1
     for x in _inputs(22):
@@ -138,12 +123,7 @@ def test_two_range_tanh_matches_libm_near_one(mc):
 def test_table_log_within_1ulp(mc):
     """LDPC_PREC_F64's table-driven log((1+T)/(1-T)) (tools/gen_logtab.py):
     within 1 ulp of glibc over T in [-1, 1], near +-1, near 0 and the edges."""
-    rng = np.random.default_rng(15)
-    Ts = [rng.uniform(-1, 1, 400_000), np.tanh(rng.normal(0, 10, 400_000)),
-          1 - 10.0 ** rng.uniform(-16, 0, 200_000), -1 + 10.0 ** rng.uniform(-16, 0, 200_000),
-          10.0 ** rng.uniform(-300, -1, 200_000),
-          np.array([1.0, -1.0, 0.0, -0.0, np.nan, 0.5, -0.5, 1 - 2.0 ** -53, -1 + 2.0 ** -53])]
-    for T in Ts:
+    for T in math_sets.table_log_sets():
         x = np.ascontiguousarray(T, np.float64)
         out = np.zeros(2, np.int64)
         mc.check_logtab(x.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(x.size),
@@ -169,19 +149,15 @@ def test_batched_divisions(mc):
     for the slots' three open check-message quotients): the same accuracy as
     the one-at-a-time forms -- within 3 ulp of glibc, and identical to them
     on these 2.4 M host operands (the residual correction squares the batched
-    reciprocal's error away); the GPU's v_rcp_f64 seed is checked by the GPU
-    parity tests."""
-    rng = np.random.default_rng(21)
-    m = np.concatenate([rng.uniform(-16, 16, 600_000), rng.normal(0, 3, 600_000),
-                        rng.uniform(-1, 1, 300_000) * 10.0 ** rng.uniform(-12, 0, 300_000)])
+    reciprocal's error away); with the GPU's v_rcp_f64 seed the same forms and
+    div_fast_n itself are held to glibc on these operands by
+    tests/test_gpu_math.py."""
+    m, T = math_sets.batched_division_operands()
     mism, maxulp = _run(mc, "check_batch", 0, m)
     assert maxulp <= 1 and mism <= m.size * 1e-3, (mism, maxulp)
     _, maxulp = _run(mc, "check_batch", 2, m)
     assert maxulp <= 3
     # open check operands: products of tanh(m/2) with |m| <= 16
-    t = np.tanh(rng.uniform(-8, 8, (1_200_000, 3)) / 1.0)
-    T = (t[:, 0] * t[:, 1] * rng.choice([1.0, 0.5, 1e-3], t.shape[0])).astype(np.float64)
-    T = np.concatenate([T, np.tanh(rng.uniform(-8, 8, 300_000))])
     mism, maxulp = _run(mc, "check_batch", 1, T)
     assert maxulp <= 1 and mism <= T.size * 1e-3, (mism, maxulp)
     _, maxulp = _run(mc, "check_batch", 3, T)
