@@ -7,6 +7,7 @@
 
 #include <chrono>
 
+#include "ldpc_arena.hpp"
 #include "ldpc_aux.hpp"
 #include "ldpc_ctx.hpp"
 
@@ -92,6 +93,28 @@ ldpc::GraphView graph_view(const ldpc_ctx *ctx) {
   return g;
 }
 
+ldpc::MsnView msn_view(const ldpc_ctx *ctx) {
+  const ldpc_ctx::Code &code = ctx->code;
+  const ldpc_ctx::Graph &gr = ctx->graph;
+  ldpc::MsnView v;
+  v.rdesc = gr.d_msnd[0];
+  v.rx = gr.d_msn[0];
+  v.cdesc = gr.d_msnd[1];
+  v.cx = gr.d_msn[1];
+  v.corig = gr.d_msn[2];
+  v.cpos = gr.d_msn[3];
+  v.M = code.M;
+  v.N = code.N;
+  v.E = code.E;
+  v.KB = code.KB;
+  v.dc_max = code.dc_max;
+  v.dv_max = code.dv_max;
+  v.rs = gr.msn.rs;
+  v.cs = gr.msn.cs;
+  v.out_var = gr.msn.out_var ? 1 : 0;
+  return v;
+}
+
 // The large-code workspace, at least `need` bytes.
 int ensure_work(ldpc_ctx *ctx, size_t need) {
   ldpc_ctx::Graph &g = ctx->graph;
@@ -119,22 +142,7 @@ int decode_graph(ldpc_ctx *ctx, const ldpc::DecodeArgs &a, int method, int preci
       return set_err(ctx, LDPC_EUNSUPPORTED,
                      "large-code min-sum needs M <= " + std::to_string(ldpc::kMsnMaxRows) +
                          " check rows (the narrow-chunk pipeline's limit)");
-    ldpc::MsnView v;
-    v.rx = gr.d_msn[0];
-    v.cx = gr.d_msn[1];
-    v.rdesc = gr.d_msnd[0];
-    v.cdesc = gr.d_msnd[1];
-    v.rs = gr.msn.rs;
-    v.cs = gr.msn.cs;
-    v.corig = gr.d_msn[2];
-    v.cpos = gr.d_msn[3];
-    v.M = g.M;
-    v.N = g.N;
-    v.E = g.E;
-    v.KB = g.KB;
-    v.dc_max = g.dc_max;
-    v.dv_max = g.dv_max;
-    v.out_var = gr.msn.out_var ? 1 : 0;
+    const ldpc::MsnView v = msn_view(ctx);
     int C = ldpc::msn_default_chunks();
     const int need_c = (a.B + ldpc::kMsnFrames - 1) / ldpc::kMsnFrames;
     if (need_c < C) C = need_c >= 8 ? (need_c + 7) / 8 * 8 : need_c;
@@ -195,6 +203,35 @@ int ensure_window_stage(ldpc_ctx *ctx, size_t need) {
   if (e != hipSuccess) return hip_err(ctx, e, "hipMalloc(window staging)");
   s.span_bytes = want;
   return LDPC_OK;
+}
+
+// What follows the span in the window staging area, for B windows: the window
+// list, the gathered frames where the large-code kernels need them, the
+// packed bytes and the syndrome weights.  Over a null base it measures.
+struct WindowTail {
+  int64_t *win;
+  float *frames;
+  uint8_t *packed;
+  int32_t *synd;
+  size_t bytes;
+};
+
+// the span's own region at the start of the area, S samples
+size_t span_bytes(int64_t S) {
+  ldpc::Arena a;
+  a.take<float>((size_t)S);
+  return a.bytes();
+}
+
+WindowTail window_tail(void *base, size_t B, int N, int KB, bool gather) {
+  ldpc::Arena a(base);
+  WindowTail t;
+  t.win = a.take<int64_t>(B);
+  t.frames = gather ? a.take<float>(B * (size_t)N) : nullptr;
+  t.packed = a.take<uint8_t>(B * (size_t)KB);
+  t.synd = a.take<int32_t>(B);
+  t.bytes = a.bytes();
+  return t;
 }
 
 // S samples in[i * elem_stride] -> pinned host stage -> d_span (enqueued on
@@ -429,28 +466,34 @@ int decode_host_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, in
   const int64_t cw = re_only ? cw_stride / 2 : cw_stride;
   const int es = re_only ? 1 : elem_stride;
   const int BO = both ? 2 * B : B;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t b_in = al((size_t)n_stage * 4), b_pk = al((size_t)BO * KB),
-               b_bits = out_bits_opt ? al((size_t)BO * N) : 0,
-               b_it = iters_used_opt ? al((size_t)BO * 4) : 0,
-               b_sy = syn_weight_opt ? al((size_t)BO * 4) : 0,
-               b_llr = llr_out_opt ? al((size_t)BO * N * 4) : 0;
+  // the device stage in one walk: the input, then the outputs side by side
+  // (measured over a null base, carved over the stage)
+  float *d_in, *d_llr;
+  uint8_t *d_pk, *d_bits;
+  int32_t *d_it, *d_sy;
+  size_t b_in = 0;
+  auto walk = [&](void *base) {
+    ldpc::Arena a(base);
+    d_in = a.take<float>((size_t)n_stage);
+    b_in = a.bytes();
+    d_pk = a.take<uint8_t>((size_t)BO * KB);
+    d_bits = out_bits_opt ? a.take<uint8_t>((size_t)BO * N) : nullptr;
+    d_it = iters_used_opt ? a.take<int32_t>((size_t)BO) : nullptr;
+    d_sy = syn_weight_opt ? a.take<int32_t>((size_t)BO) : nullptr;
+    d_llr = llr_out_opt ? a.take<float>((size_t)BO * N) : nullptr;
+    return a.bytes();
+  };
+  const size_t b_all = walk(nullptr);
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
-  rc = ensure_stage(ctx, b_in + b_pk + b_bits + b_it + b_sy + b_llr);
+  rc = ensure_stage(ctx, b_all);
   if (rc != LDPC_OK) return rc;
   // the pinned stage carries the input in and, after the kernel (stream
   // order), every output back in one copy of the adjacent device outputs
-  const size_t b_out = b_pk + b_bits + b_it + b_sy + b_llr;
+  const size_t b_out = b_all - b_in;
   rc = ensure_host_stage(ctx, std::max((size_t)n_stage * 4, b_out));
   if (rc != LDPC_OK) return rc;
-  char *base = (char *)ctx->stage.d;
-  float *d_in = (float *)base;
-  uint8_t *d_pk = (uint8_t *)(base + b_in);
-  uint8_t *d_bits = out_bits_opt ? (uint8_t *)(base + b_in + b_pk) : nullptr;
-  int32_t *d_it = iters_used_opt ? (int32_t *)(base + b_in + b_pk + b_bits) : nullptr;
-  int32_t *d_sy = syn_weight_opt ? (int32_t *)(base + b_in + b_pk + b_bits + b_it) : nullptr;
-  float *d_llr = llr_out_opt ? (float *)(base + b_in + b_pk + b_bits + b_it + b_sy) : nullptr;
+  walk(ctx->stage.d);
   float *h = ctx->stage.h;
   if (re_only)
     for (int64_t i = 0; i < n_stage; ++i) h[i] = in[2 * i];
@@ -473,14 +516,15 @@ int decode_host_impl(ldpc_ctx *ctx, int method, int max_iters, int et_period, in
   const char *ho = (const char *)h;
   struct {
     void *dst;
-    size_t off, n;
-  } back[] = {{out_packed, 0, (size_t)BO * KB},
-              {out_bits_opt, b_pk, (size_t)BO * N},
-              {iters_used_opt, b_pk + b_bits, (size_t)BO * 4},
-              {syn_weight_opt, b_pk + b_bits + b_it, (size_t)BO * 4},
-              {llr_out_opt, b_pk + b_bits + b_it + b_sy, (size_t)BO * N * 4}};
+    const void *src;  // on the device; the pinned copy starts at d_pk
+    size_t n;
+  } back[] = {{out_packed, d_pk, (size_t)BO * KB},
+              {out_bits_opt, d_bits, (size_t)BO * N},
+              {iters_used_opt, d_it, (size_t)BO * 4},
+              {syn_weight_opt, d_sy, (size_t)BO * 4},
+              {llr_out_opt, d_llr, (size_t)BO * N * 4}};
   for (auto &c : back)
-    if (c.dst) memcpy(c.dst, ho + c.off, c.n);
+    if (c.dst) memcpy(c.dst, ho + ((const char *)c.src - (const char *)d_pk), c.n);
   return LDPC_OK;
 }
 
@@ -496,14 +540,12 @@ int ldpc_stage_span(ldpc_ctx *ctx, const float *in, int64_t n_in_floats, int ele
   if (!in || elem_stride < 1 || n_in_floats < 0 || max_windows < 0)
     return set_err(ctx, LDPC_EINVAL, "bad span");
   const int64_t S = (n_in_floats + elem_stride - 1) / elem_stride;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t B = (size_t)max_windows;
   // room for that many windows' lists and outputs behind the span
-  const size_t extra = al(B * 8) + (ctx->graph.on ? al(B * (size_t)ctx->code.N * 4) : 0) +
-                       al(B * (size_t)ctx->code.KB) + al(B * 4);
+  const size_t extra =
+      window_tail(nullptr, (size_t)max_windows, ctx->code.N, ctx->code.KB, ctx->graph.on).bytes;
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
-  int rc = ensure_window_stage(ctx, al((size_t)S * 4) + extra);
+  int rc = ensure_window_stage(ctx, span_bytes(S) + extra);
   if (rc != LDPC_OK) return rc;
   return copy_span(ctx, in, S, elem_stride, (float *)ctx->stage.d_span);
 }
@@ -526,21 +568,18 @@ int ldpc_decode_windows(ldpc_ctx *ctx, int method, int max_iters, int et_period,
   for (int b = 0; b < B; ++b)
     if (win[b] < 0 || (win[b] >> 1) + N > S)
       return set_err(ctx, LDPC_EINVAL, "window outside the input span");
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  // the on-chip kernels read each window in place, like the small-code ones
+  // the on-chip kernels read each window in place, like the small-code ones;
+  // gathered frames: only the large-code kernels need them
   const bool gather = ctx->graph.on && !(ctx->onchip.on && (method == 0 || method == 1));
-  const size_t b_span = al((size_t)S * 4), b_win = al((size_t)B * 8),
-               // gathered frames: only the large-code kernels need them
-               b_fr = gather ? al((size_t)B * N * 4) : 0, b_pk = al((size_t)B * KB),
-               b_sy = al((size_t)B * 4);
+  const size_t tail_bytes = window_tail(nullptr, (size_t)B, N, KB, gather).bytes;
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return hip_err(ctx, e, "hipSetDevice");
-  rc = ensure_window_stage(ctx, b_span + b_win + b_fr + b_pk + b_sy);
+  rc = ensure_window_stage(ctx, span_bytes(S) + tail_bytes);
   if (rc != LDPC_OK) return rc;
   // pinned: the window list in, then the packed words and syndrome weights
   // out in one copy (d_pk .. d_sy are adjacent in the staging area), so no
-  // transfer goes through a pageable bounce
-  const size_t h_need = b_win + b_pk + b_sy;
+  // transfer goes through a pageable bounce: the same tail without the frames
+  const size_t h_need = window_tail(nullptr, (size_t)B, N, KB, false).bytes;
   if (h_need > sg.h_win_bytes) {
     if (sg.h_win) {
       (void)hipStreamSynchronize(ctx->stream);
@@ -557,13 +596,10 @@ int ldpc_decode_windows(ldpc_ctx *ctx, int method, int max_iters, int et_period,
   }
   // the span sits at the start of the staging area; a reused span must be the
   // one staged last, with the same length (then it ends before span_cap)
-  char *base = (char *)sg.d_span;
-  const size_t span_cap = sg.span_bytes - (b_win + b_fr + b_pk + b_sy);
-  float *d_span = (float *)base;
-  int64_t *d_win = (int64_t *)(base + span_cap);
-  float *d_fr = (float *)(base + span_cap + b_win);
-  uint8_t *d_pk = (uint8_t *)(base + span_cap + b_win + b_fr);
-  int32_t *d_sy = (int32_t *)(base + span_cap + b_win + b_fr + b_pk);
+  const size_t span_cap = sg.span_bytes - tail_bytes;
+  float *d_span = (float *)sg.d_span;
+  WindowTail dt = window_tail((char *)sg.d_span + span_cap, (size_t)B, N, KB, gather);
+  const WindowTail ht = window_tail(sg.h_win, (size_t)B, N, KB, false);
   const auto tnow = []() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
   };
@@ -578,8 +614,7 @@ int ldpc_decode_windows(ldpc_ctx *ctx, int method, int max_iters, int et_period,
     t0 = t1;
   }
   // the previous call's copy out of h_win has completed (it synchronised)
-  memcpy(sg.h_win, win, (size_t)B * 8);
-  uint8_t *h_out = (uint8_t *)sg.h_win + b_win;
+  memcpy(ht.win, win, (size_t)B * 8);
   // Small codes: the kernel reads the (pinned, mapped) window list and writes
   // its packed bytes and syndrome weights into pinned memory itself -- a few
   // bytes per window over the bus, and no DMA round trip on a launch whose
@@ -589,27 +624,27 @@ int ldpc_decode_windows(ldpc_ctx *ctx, int method, int max_iters, int et_period,
     void *dv = nullptr;
     if ((e = hipHostGetDevicePointer(&dv, sg.h_win, 0)) != hipSuccess)
       return hip_err(ctx, e, "hipHostGetDevicePointer(windows)");
-    d_win = (int64_t *)dv;
-    d_pk = (uint8_t *)dv + b_win;
-    d_sy = (int32_t *)((uint8_t *)dv + b_win + b_pk);
-  } else if ((e = hipMemcpyAsync(d_win, sg.h_win, (size_t)B * 8, hipMemcpyHostToDevice,
+    dt = window_tail(dv, (size_t)B, N, KB, false);
+  } else if ((e = hipMemcpyAsync(dt.win, ht.win, (size_t)B * 8, hipMemcpyHostToDevice,
                                  ctx->stream)) != hipSuccess) {
     return hip_err(ctx, e, "hipMemcpyAsync(windows)");
   }
   if (gather) {  // the large-code kernels read frames at a fixed stride: gather first
-    if (ldpc::launch_gather_windows(d_span, d_win, B, N, d_fr, ctx->stream) != 0)
+    if (ldpc::launch_gather_windows(d_span, dt.win, B, N, dt.frames, ctx->stream) != 0)
       return set_err(ctx, LDPC_EDEVICE, "gather_windows launch failed");
-    rc = decode_device_impl(ctx, method, max_iters, et_period, precision, d_fr, N, 1, 1.0f, B,
-                            0, d_pk, nullptr, nullptr, syn_weight_opt ? d_sy : nullptr, nullptr,
-                            ctx->stream);
+    rc = decode_device_impl(ctx, method, max_iters, et_period, precision, dt.frames, N, 1, 1.0f,
+                            B, 0, dt.packed, nullptr, nullptr, syn_weight_opt ? dt.synd : nullptr,
+                            nullptr, ctx->stream);
   } else {  // the small-code kernels read each window in place (DecodeArgs::win)
     rc = decode_device_impl(ctx, method, max_iters, et_period, precision, d_span, N, 1, 1.0f, B,
-                            0, d_pk, nullptr, nullptr, syn_weight_opt ? d_sy : nullptr, nullptr,
-                            ctx->stream, d_win);
+                            0, dt.packed, nullptr, nullptr, syn_weight_opt ? dt.synd : nullptr,
+                            nullptr, ctx->stream, dt.win);
   }
   if (rc != LDPC_OK) return rc;
-  const size_t out_bytes = syn_weight_opt ? b_pk + (size_t)B * 4 : (size_t)B * KB;
-  if (!direct && (e = hipMemcpyAsync(h_out, d_pk, out_bytes, hipMemcpyDeviceToHost,
+  // packed bytes alone, or through the syndrome weights behind them
+  const size_t out_bytes =
+      syn_weight_opt ? (size_t)((uint8_t *)(ht.synd + B) - ht.packed) : (size_t)B * KB;
+  if (!direct && (e = hipMemcpyAsync(ht.packed, dt.packed, out_bytes, hipMemcpyDeviceToHost,
                                      ctx->stream)) != hipSuccess)
     return hip_err(ctx, e, "hipMemcpyAsync(out)");
   if (sg.profile) {
@@ -626,8 +661,8 @@ int ldpc_decode_windows(ldpc_ctx *ctx, int method, int max_iters, int et_period,
     sg.prof[2] += t1 - t0;
     t0 = t1;
   }
-  memcpy(out_packed, h_out, (size_t)B * KB);
-  if (syn_weight_opt) memcpy(syn_weight_opt, h_out + b_pk, (size_t)B * 4);
+  memcpy(out_packed, ht.packed, (size_t)B * KB);
+  if (syn_weight_opt) memcpy(syn_weight_opt, ht.synd, (size_t)B * 4);
   if (sg.profile) {
     sg.prof[3] += tnow() - t0;
     sg.calls += 1;

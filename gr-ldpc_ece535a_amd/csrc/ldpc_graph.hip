@@ -29,7 +29,9 @@
 // 2E x sizeof(Real) read + 2E x sizeof(Real) written + 4N channel bytes.  A stopped chunk costs one flag read per block.
 //
 // The per-edge arithmetic is the reference's, in its order, with the same
-// Math<PREC> as the small-code kernel (ldpc_device.hpp).
+// Math<PREC> as the small-code kernel (ldpc_device.hpp).  The workspace these
+// kernels index is laid out on the host (ldpc_graph_work.cc); rows and columns
+// per wave are constants of ldpc_graph.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,22 +44,11 @@
 namespace ldpc {
 namespace {
 
-#ifndef LDPC_GRAPH_ROWS_PER_WAVE
-#define LDPC_GRAPH_ROWS_PER_WAVE 4
-#endif
-#ifndef LDPC_GRAPH_COLS_PER_WAVE
-#define LDPC_GRAPH_COLS_PER_WAVE 4
-#endif
-constexpr int kRowsPerWave = LDPC_GRAPH_ROWS_PER_WAVE;
-constexpr int kColsPerWave = LDPC_GRAPH_COLS_PER_WAVE;
-
 __device__ __forceinline__ int wave_in_block() {
   return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 }
 
 __device__ __forceinline__ uint64_t bit_of(uint64_t w, int lane) { return (w >> lane) & 1ull; }
-
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Element x (an edge or a column) of frame lane in chunk k: chunk-major, so
 // one chunk's values of consecutive edges are consecutive 64-lane blocks
@@ -153,7 +144,7 @@ __global__ void __launch_bounds__(256) g_load(GraphView g, GraphWork w_, const f
   }
 }
 
-// Horizontal step for kRowsPerWave rows x 64 frames per wave.  For h > 0 the
+// Horizontal step for kGraphRowsPerWave rows x 64 frames per wave.  For h > 0 the
 // same pass evaluates checkFrame's rows (:236-253) on the hard decision of
 // iteration h-1: 64 frames per XOR of packed words.
 template <int PREC, int DC>
@@ -172,12 +163,12 @@ __global__ void __launch_bounds__(256) g_check(GraphView g, GraphWork w_, int h)
   const Real *Q = (const Real *)w.Q + at(0, k, g.E, lane);
   Real *R = (Real *)w.R + at(0, k, g.E, lane);
   const int wg = blockIdx.x * 4 + wave_in_block();
-  const int j0 = wg * kRowsPerWave;
+  const int j0 = wg * kGraphRowsPerWave;
   // parities first: their scalar loads then issue back to back instead of
   // queueing behind each row's message stores
   uint64_t odd = 0;
   if (h > 0) {
-    const int j1 = min(j0 + kRowsPerWave, g.M);
+    const int j1 = min(j0 + kGraphRowsPerWave, g.M);
     for (int j = j0; j < j1; ++j) {
       uint64_t par = 0;
       const int e1 = g.rp[j + 1];
@@ -185,7 +176,7 @@ __global__ void __launch_bounds__(256) g_check(GraphView g, GraphWork w_, int h)
       odd |= par;
     }
   }
-  for (int jj = 0; jj < kRowsPerWave; ++jj) {
+  for (int jj = 0; jj < kGraphRowsPerWave; ++jj) {
     const int j = j0 + jj;
     if (j >= g.M) break;
     const int e0 = g.rp[j], d = g.rp[j + 1] - e0;
@@ -215,9 +206,9 @@ __global__ void __launch_bounds__(256) g_check_bf(GraphView g, GraphWork w_, int
   if (w.chunk_done[k]) return;
   const int64_t chunks = w.chunks;
   const int wg = blockIdx.x * 4 + wave_in_block();
-  const int j0 = wg * kRowsPerWave;
+  const int j0 = wg * kGraphRowsPerWave;
   uint64_t odd = 0;
-  for (int jj = 0; jj < kRowsPerWave; ++jj) {
+  for (int jj = 0; jj < kGraphRowsPerWave; ++jj) {
     const int j = j0 + jj;
     if (j >= g.M) break;
     const int e0 = g.rp[j], d = g.rp[j + 1] - e0;
@@ -259,7 +250,7 @@ __global__ void __launch_bounds__(256) g_decide(GraphWork w, int h, int max_iter
   }
 }
 
-// Vertical step for kColsPerWave columns x 64 frames per wave (sum-product):
+// Vertical step for kGraphColsPerWave columns x 64 frames per wave (sum-product):
 // L = sum_j (E(j,i) + r) (:519-532), vhat = L <= 0, and
 // M(j,i) = sum_{k != j} (E(k,i) + r) (:540-553), both ascending.
 template <typename Real, int DV>
@@ -273,8 +264,8 @@ __global__ void __launch_bounds__(256) g_var(GraphView g, GraphWork w_) {
   const bool frozen = bit_of(done, lane) != 0;
   const Real *R = (const Real *)w.R + at(0, k, g.E, lane);
   Real *Q = (Real *)w.Q + at(0, k, g.E, lane);
-  const int c0 = (blockIdx.x * 4 + wave_in_block()) * kColsPerWave;
-  for (int cc = 0; cc < kColsPerWave; ++cc) {
+  const int c0 = (blockIdx.x * 4 + wave_in_block()) * kGraphColsPerWave;
+  for (int cc = 0; cc < kGraphColsPerWave; ++cc) {
     const int c = c0 + cc;
     if (c >= g.N) break;
     const int k0 = g.cp[c], d = g.cp[c + 1] - k0;
@@ -324,8 +315,8 @@ __global__ void __launch_bounds__(256) g_var_bf(GraphView g, GraphWork w_) {
   const int64_t chunks = w.chunks;
   const uint64_t done = w.done_w[k];
   const int half = (int)((unsigned)g.M / 2u);
-  const int c0 = (blockIdx.x * 4 + wave_in_block()) * kColsPerWave;
-  for (int cc = 0; cc < kColsPerWave; ++cc) {
+  const int c0 = (blockIdx.x * 4 + wave_in_block()) * kGraphColsPerWave;
+  for (int cc = 0; cc < kGraphColsPerWave; ++cc) {
     const int c = c0 + cc;
     if (c >= g.N) break;
     const int k0 = g.cp[c], d = g.cp[c + 1] - k0;
@@ -347,9 +338,9 @@ __global__ void __launch_bounds__(256) g_synd(GraphView g, GraphWork w_, int B) 
   const int lane = threadIdx.x & 63;
   const int64_t chunks = w.chunks;
   const int64_t b = (int64_t)k * 64 + lane;
-  const int j0 = (blockIdx.x * 4 + wave_in_block()) * kRowsPerWave;
+  const int j0 = (blockIdx.x * 4 + wave_in_block()) * kGraphRowsPerWave;
   int cnt = 0;
-  for (int jj = 0; jj < kRowsPerWave; ++jj) {
+  for (int jj = 0; jj < kGraphRowsPerWave; ++jj) {
     const int j = j0 + jj;
     if (j >= g.M) break;
     const int e0 = g.rp[j], d = g.rp[j + 1] - e0;
@@ -634,70 +625,7 @@ void run_sp(const GraphView &g, const GraphWork &w, const DecodeArgs &a, dim3 rg
   }
 }
 
-int check_waves(const GraphView &g) {
-  return 4 * ((g.M + 4 * kRowsPerWave - 1) / (4 * kRowsPerWave));
-}
-
 }  // namespace
-
-size_t graph_work_bytes(const GraphView &g, int Bp, int prec, int method, bool want_post) {
-  const size_t real = prec == 1 ? 4 : 8;
-  const bool soft = method == 0 || method == 1;
-  const size_t chunks = (size_t)Bp / 64;
-  size_t n = 0;
-  if (soft) n += 2 * al256((size_t)g.E * Bp * real) + al256((size_t)g.N * Bp * 4);
-  n += al256((size_t)g.N * chunks * 8);                                   // hard
-  if (!soft) n += al256((size_t)g.N * chunks * 8) + al256((size_t)g.M * chunks * 8);  // y, rowpar
-  n += al256((size_t)check_waves(g) * chunks * 8) + al256(chunks * 8) + al256(chunks);
-  n += 2 * al256((size_t)Bp * 4);
-  if (want_post) n += al256((size_t)g.N * Bp * 4);
-  // compaction: state, perm x2, src, spare L / post / hard
-  n += al256(sizeof(GraphState)) + 3 * al256((size_t)Bp * 4) + al256((size_t)g.N * chunks * 8);
-  if (soft) n += al256((size_t)g.N * Bp * 4) + (want_post ? al256((size_t)g.N * Bp * 4) : 0);
-  return n;
-}
-
-void graph_work_carve(GraphWork &w, void *base, const GraphView &g, int Bp, int prec, int method,
-                      bool want_post) {
-  const size_t real = prec == 1 ? 4 : 8;
-  const bool soft = method == 0 || method == 1;
-  const size_t chunks = (size_t)Bp / 64;
-  char *p = (char *)base;
-  auto take = [&](size_t bytes) {
-    char *r = p;
-    p += al256(bytes);
-    return (void *)r;
-  };
-  w = GraphWork{};
-  w.Bp = Bp;
-  w.chunks = (int)chunks;
-  w.check_waves = check_waves(g);
-  if (soft) {
-    w.Q = take((size_t)g.E * Bp * real);
-    w.R = take((size_t)g.E * Bp * real);
-    w.L = (float *)take((size_t)g.N * Bp * 4);
-  }
-  w.hard = (uint64_t *)take((size_t)g.N * chunks * 8);
-  if (!soft) {
-    w.y = (uint64_t *)take((size_t)g.N * chunks * 8);
-    w.rowpar = (uint64_t *)take((size_t)g.M * chunks * 8);
-  }
-  w.synd_part = (uint64_t *)take((size_t)w.check_waves * chunks * 8);
-  w.done_w = (uint64_t *)take(chunks * 8);
-  w.chunk_done = (uint8_t *)take(chunks);
-  w.used = (int32_t *)take((size_t)Bp * 4);
-  w.synd = (int32_t *)take((size_t)Bp * 4);
-  w.post = want_post ? (float *)take((size_t)g.N * Bp * 4) : nullptr;
-  w.st = (GraphState *)take(sizeof(GraphState));
-  w.perm = (int32_t *)take((size_t)Bp * 4);
-  w.perm2 = (int32_t *)take((size_t)Bp * 4);
-  w.src = (int32_t *)take((size_t)Bp * 4);
-  w.hard2 = (uint64_t *)take((size_t)g.N * chunks * 8);
-  if (soft) {
-    w.L2 = (float *)take((size_t)g.N * Bp * 4);
-    w.post2 = want_post ? (float *)take((size_t)g.N * Bp * 4) : nullptr;
-  }
-}
 
 int launch_graph_decode(const GraphView &g, const GraphWork &w, const DecodeArgs &a, int method,
                         int prec, void *stream) {
@@ -707,7 +635,7 @@ int launch_graph_decode(const GraphView &g, const GraphWork &w, const DecodeArgs
   hipStream_t st = (hipStream_t)stream;
   const int chunks = w.chunks;
   const dim3 rgrid(w.check_waves / 4, chunks);
-  const dim3 cgrid((g.N + 4 * kColsPerWave - 1) / (4 * kColsPerWave), chunks);
+  const dim3 cgrid((g.N + 4 * kGraphColsPerWave - 1) / (4 * kGraphColsPerWave), chunks);
   const dim3 tgrid((g.N + 63) / 64, chunks);
   const bool soft = method == 0 || method == 1;
   g_reset<<<chunks, 64, 0, st>>>(w, a.B, method == 3 ? 0 : a.max_iters);

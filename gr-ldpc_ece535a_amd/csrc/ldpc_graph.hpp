@@ -24,6 +24,13 @@ namespace ldpc {
 
 constexpr int kGraphDcMax = 32;  // check degree limit of the large-code kernels
 constexpr int kGraphDvMax = 16;  // variable degree limit
+// check rows / columns a wave of g_check / g_var takes, 64 frames of each
+constexpr int kGraphRowsPerWave = 4;
+constexpr int kGraphColsPerWave = 4;
+// waves of the check pass (blocks of 4): one synd_part word each per chunk
+constexpr int graph_check_waves(int M) {
+  return 4 * ((M + 4 * kGraphRowsPerWave - 1) / (4 * kGraphRowsPerWave));
+}
 
 struct GraphView {
   const int32_t *rp;  // M + 1 row offsets into the CSR edge list
@@ -72,9 +79,10 @@ struct GraphWork {
   int Bp, chunks, check_waves;
 };
 
-// Bytes of workspace for Bp frames (Bp a multiple of 64).
+// The workspace for Bp frames (Bp a multiple of 64), one walk of its regions
+// (ldpc_graph_work.cc): graph_work_bytes() measures it, graph_work_carve()
+// lays a buffer of that many bytes out at base.
 size_t graph_work_bytes(const GraphView &g, int Bp, int prec, int method, bool want_post);
-// Lays a workspace of graph_work_bytes() bytes out at base.
 void graph_work_carve(GraphWork &w, void *base, const GraphView &g, int Bp, int prec,
                       int method, bool want_post);
 // Decodes args.B <= w.Bp frames (all launches enqueued on `stream`).
@@ -84,10 +92,11 @@ int launch_graph_decode(const GraphView &g, const GraphWork &w, const DecodeArgs
 
 // ---- min-sum with the gathered state in one XCD's L2 (ldpc_graph_msn.hip):
 // chunks of kMsnFrames frames, XCD-aware chunk placement, storage order ------
-#ifndef LDPC_MSN_FRAMES
-#define LDPC_MSN_FRAMES 2
-#endif
-constexpr int kMsnFrames = LDPC_MSN_FRAMES;
+constexpr int kMsnFrames = 2;  // frames per chunk
+constexpr int kMsnIB = 256;    // rows / columns per 256-thread block (one per lane)
+// With 2 frames per chunk an edge's alpha bits (2 per frame) take a nibble:
+// slots 2u and 2u + 1 of a row share byte u, so a row has this many bytes
+constexpr int msn_alpha_rows(int dc_max) { return (dc_max + 1) / 2; }
 // rows the pipeline takes: the check pass's fused decision counts a chunk's
 // blocks of 256 rows in 12-bit fields (and rows fit the edge words' 24 bits)
 constexpr int kMsnMaxRows = 4095 * 256;
@@ -127,10 +136,8 @@ struct MsnView {
   int out_var;           // outputs written by the variable pass (MsnTables::out_var)
 };
 
-struct MsnTables {  // host copies of MsnView's arrays
-  // full slot-major tables (D x n, -1 past the degree): rcs[t][p] storage
-  // column of row p's t-th edge, crs[t][x] storage row | place << 24
-  std::vector<int32_t> rp, cp, rcs, crs, corig, cpos;
+struct MsnTables {  // host copies of MsnView's arrays, and what is reported
+  std::vector<int32_t> corig, cpos;
   std::vector<int32_t> rx, cx;  // explicit values (MsnView)
   std::vector<MsnDesc> rdesc, cdesc;
   int rs = 0, cs = 0;
@@ -141,7 +148,7 @@ struct MsnTables {  // host copies of MsnView's arrays
 };
 
 struct MsnWork {
-  int S, chunks, nb_check, nb_var, check_waves, real_bytes, out_var;
+  int S, chunks, nb_check, nb_var, real_bytes, out_var;
   float *L;          // chunks x N x F: Lci = -tx
   void *LQ;          // chunks x N x F Real: Lci + sum of the column's L(r)
   void *m1, *m2;     // chunks x M x F Real
@@ -157,10 +164,12 @@ struct MsnWork {
   int32_t *ctrl;     // [0] next frame of the batch, [1] frames finished
 };
 
+// The storage order and its tables (ldpc_msn_tables.cc; throws
+// std::runtime_error if the descriptors' self-check fails).
 void msn_build(int M, int N, const std::vector<int32_t> &rp, const std::vector<int32_t> &ci,
                MsnTables &t);
-void msn_tables(int M, int N, const std::vector<int32_t> &rp0, const std::vector<int32_t> &ci0,
-                const std::vector<int32_t> &rpos, const std::vector<int32_t> &cpos, MsnTables &t);
+// Chunks in flight by default (LDPC_MSN_CHUNKS), and the workspace for
+// `chunks` chunks as one walk, measured or carved (ldpc_graph_work.cc).
 int msn_default_chunks();
 size_t msn_work_bytes(const MsnView &g, int chunks, int prec);
 void msn_work_carve(MsnWork &w, void *base, const MsnView &g, int chunks, int prec);

@@ -6,8 +6,8 @@
 // 2-bit alpha per edge (the compressed messages of the round-2 64-frame
 // pipeline, retired in round 4), laid out for the cache hierarchy:
 //
-// * Narrow chunks.  A chunk holds F = kF frames (2 since round 4; element x
-//   of frame f at (k * n + x) * F + f), so the tables a pass gathers from --
+// * Narrow chunks.  A chunk holds F = kF = 2 frames (element x of frame f at
+//   (k * n + x) * F + f), so the tables a pass gathers from --
 //   LQ in the check pass (8 N F bytes = 1.05 MB for N = 64800 at F = 2), the
 //   row state {m1, m2, meta} in the variable pass (17 M F = 1.1 MB) -- fit
 //   one XCD's 4 MiB L2.  With 64-frame chunks they were 33-35 MB, every
@@ -18,7 +18,7 @@
 //   through its chunks one after another and a chunk's table is gathered
 //   by the CUs whose L2 holds it.
 // * Storage order.  Rows and columns are stored in an order chosen on the
-//   host (ldpc_msn_build): for codes with the DVB-S2 structure (IRA, 360-
+//   host (msn_build, ldpc_msn_tables.cc): for codes with the DVB-S2 structure (IRA, 360-
 //   column groups, row r = x + s q mod M) rows by residue class mod q, which
 //   makes every circulant a shifted identity, so the 64 rows of a wave read
 //   (runs of) consecutive columns for each of their edges and the 64 columns
@@ -38,14 +38,14 @@
 // that completes the chunk) -> msn_var (outputs of the stopped frames, the vertical
 // step, refills); separate msn_post / msn_cols launches for the outputs only
 // for codes outside that fast path.
+//
+// This file holds the kernels and their launches.  The storage order and the
+// edge descriptors are built on the host in ldpc_msn_tables.cc, the workspace
+// is laid out in ldpc_graph_work.cc; the constants both sides share (frames
+// per chunk, items per block, alpha bytes per row) are in ldpc_graph.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <stdexcept>
-#include <vector>
-
-#include <stdio.h>
-#include <stdlib.h>
 
 #include "ldpc_device.hpp"
 #include "ldpc_graph.hpp"
@@ -55,8 +55,6 @@ namespace ldpc {
 namespace {
 
 constexpr int kF = kMsnFrames;  // frames per chunk
-constexpr int kIB = 256;        // rows / columns per 256-thread block (one per lane)
-static_assert(kF == 2 || kF == 4, "frames per chunk: 2 or 4");
 
 // Workgroup b -> (chunk, block of the chunk).  With a multiple of 8 chunks,
 // chunk k's blocks run on XCD k mod 8 (the dispatcher deals workgroups to the
@@ -95,57 +93,14 @@ template <typename Real>
 __device__ __forceinline__ void stv(Real *p, const Vec<Real> &x) {
   *(Vec<Real> *)p = x;
 }
-// The same, non-temporal, for the state a pass streams once (row state in the
-// check pass, L and LQ in the variable pass) -- meant to keep the gathered
-// table and the edge tables in L2.  Measured slower (config 4: 1 973 vs
-// 2 212 Mbit/s, profiles/round3/msn/ab_nt.txt), so off unless built with
-// -DLDPC_MSN_NT=1.
-#ifndef LDPC_MSN_NT
-#define LDPC_MSN_NT 0
-#endif
-template <typename Real>
-__device__ __forceinline__ Vec<Real> ldv_nt(const Real *p) {
-#if LDPC_MSN_NT
-  typedef Real V __attribute__((ext_vector_type(kF)));
-  const V v = __builtin_nontemporal_load((const V *)p);
-  Vec<Real> r;
-#pragma unroll
-  for (int j = 0; j < kF; ++j) r.v[j] = v[j];
-  return r;
-#else
-  return ldv(p);
-#endif
-}
-template <typename Real>
-__device__ __forceinline__ void stv_nt(Real *p, const Vec<Real> &x) {
-#if LDPC_MSN_NT
-  typedef Real V __attribute__((ext_vector_type(kF)));
-  V v;
-#pragma unroll
-  for (int j = 0; j < kF; ++j) v[j] = x.v[j];
-  __builtin_nontemporal_store(v, (V *)p);
-#else
-  stv(p, x);
-#endif
-}
-typedef uint32_t MetaWord;  // F meta bytes (F <= 4)
-__device__ __forceinline__ MetaWord ld_meta(const uint8_t *p) {
-  if constexpr (kF == 4) return *(const uint32_t *)p;
-  else return *(const uint16_t *)p;
-}
-__device__ __forceinline__ void st_meta(uint8_t *p, MetaWord m) {
-  if constexpr (kF == 4) *(uint32_t *)p = m;
-  else *(uint16_t *)p = (uint16_t)m;
-}
+typedef uint32_t MetaWord;  // F meta bytes
+__device__ __forceinline__ MetaWord ld_meta(const uint8_t *p) { return *(const uint16_t *)p; }
+__device__ __forceinline__ void st_meta(uint8_t *p, MetaWord m) { *(uint16_t *)p = (uint16_t)m; }
 
 // alpha of an edge for frame f from the chunk's byte: bit 2f L(q) < 0, bit
 // 2f+1 sign 0 (:338, sign(0) = sign(NaN) = 0)
-// With 2 frames per chunk an edge's alpha bits take a nibble: slots 2u and
-// 2u + 1 of a row share byte u ([u][p] per chunk), half the bytes.
-constexpr bool kAlphaNibbles = kF == 2;
-__host__ __device__ __forceinline__ int alpha_rows(int dc_max) {
-  return kAlphaNibbles ? (dc_max + 1) / 2 : dc_max;
-}
+// An edge's alpha bits take a nibble: slots 2u and 2u + 1 of a row share
+// byte u ([u][p] per chunk, msn_alpha_rows(dc_max) bytes per row).
 __device__ __forceinline__ int alpha_of(uint32_t byte, int f) {
   const uint32_t b = byte >> (2 * f);
   return (b & 2u) ? 0 : ((b & 1u) ? -1 : 1);
@@ -263,7 +218,7 @@ __device__ __forceinline__ void check_row(const MsnView &g, const MsnWork &w, in
   Real *m1 = (Real *)w.m1, *m2 = (Real *)w.m2;
   const Real *LQ = (const Real *)w.LQ;
   const int64_t ro = el(k, g.M, p);
-  uint8_t *alpha = w.alpha + (int64_t)k * alpha_rows(g.dc_max) * g.M + p;  // [t][p] / [t/2][p]
+  uint8_t *alpha = w.alpha + (int64_t)k * msn_alpha_rows(g.dc_max) * g.M + p;  // [t/2][p]
   Vec<Real> lq[D];
 #pragma unroll
   for (int t = 0; t < D; ++t) lq[t] = ldv(LQ + el(k, g.N, cs[t]));
@@ -306,19 +261,13 @@ __device__ __forceinline__ void check_row(const MsnView &g, const MsnWork &w, in
     n2.v[f] = a2;
     nmt |= (MetaWord)(((P + 1) << 6) | (i1 + 1)) << (8 * f);
   }
-  stv_nt(m1 + ro, n1);
-  stv_nt(m2 + ro, n2);
+  stv(m1 + ro, n1);
+  stv(m2 + ro, n2);
   st_meta(w.meta + ro, nmt);
-  if constexpr (kAlphaNibbles) {
 #pragma unroll
-    for (int u = 0; 2 * u < D; ++u)
-      if (ok[2 * u])
-        alpha[(int64_t)u * g.M] = (uint8_t)(nb[2 * u] | (2 * u + 1 < D ? nb[2 * u + 1] << 4 : 0u));
-  } else {
-#pragma unroll
-    for (int t = 0; t < D; ++t)
-      if (ok[t]) alpha[(int64_t)t * g.M] = (uint8_t)nb[t];
-  }
+  for (int u = 0; 2 * u < D; ++u)
+    if (ok[2 * u])
+      alpha[(int64_t)u * g.M] = (uint8_t)(nb[2 * u] | (2 * u + 1 < D ? nb[2 * u + 1] << 4 : 0u));
 }
 
 // One row per lane, the chunk's F frames in the lane.  Frames whose slot is
@@ -329,25 +278,15 @@ __device__ __forceinline__ void check_row(const MsnView &g, const MsnWork &w, in
 // per frame f, "a row of these blocks is unsatisfied" (bits 12(f+1)..), in
 // two levels (8 group words per chunk, then the chunk's word); no fence and
 // no waiting (a chunk that is not live decides in its block 0 alone).
-#ifndef LDPC_MSN_ZIGZAG
-#define LDPC_MSN_ZIGZAG 1  // the variable pass walks each XCD's chunks backwards
-#endif
-// occupancy hints (waves per SIMD; A/B knobs)
-#ifndef LDPC_MSN_CHECK_MINB
-#define LDPC_MSN_CHECK_MINB 1
-#endif
-#ifndef LDPC_MSN_VAR_MINB
-#define LDPC_MSN_VAR_MINB 1
-#endif
 template <int PREC, int DC>
-__global__ void __launch_bounds__(256, LDPC_MSN_CHECK_MINB) msn_check(MsnView g, MsnWork w, int mbuf, int max_iters,
-                                                 int et_period, int B, int32_t *synd) {
+__global__ void __launch_bounds__(256, 1) msn_check(MsnView g, MsnWork w, int mbuf, int max_iters,
+                                                    int et_period, int B, int32_t *synd) {
   typedef typename Math<PREC>::Real Real;
   int k, bi;
   map_block(blockIdx.x, w.chunks, w.nb_check, k, bi);
   // every load that does not depend on the descriptors goes out with them:
   // one memory round trip before the gathers (rows past M load row M - 1)
-  const int p = bi * kIB + threadIdx.x;  // row storage position
+  const int p = bi * kMsnIB + threadIdx.x;  // row storage position
   const int pl = min(p, g.M - 1);
   int word[(DC + 7) / 8];
   desc_words(g.rdesc, bi, g.rs, word);
@@ -356,20 +295,15 @@ __global__ void __launch_bounds__(256, LDPC_MSN_CHECK_MINB) msn_check(MsnView g,
 #pragma unroll
   for (int f = 0; f < kF; ++f) itf[f] = ld_uniform(&w.it[k * kF + f]);
   const int64_t ro = el(k, g.M, pl);
-  const Vec<Real> om1 = ldv_nt((const Real *)w.m1 + ro), om2 = ldv_nt((const Real *)w.m2 + ro);
+  const Vec<Real> om1 = ldv((const Real *)w.m1 + ro), om2 = ldv((const Real *)w.m2 + ro);
   const MetaWord omt = ld_meta(w.meta + ro);
   uint32_t ab[DC];
-  const uint8_t *alpha = w.alpha + (int64_t)k * alpha_rows(g.dc_max) * g.M + pl;
-  if constexpr (kAlphaNibbles) {
+  const uint8_t *alpha = w.alpha + (int64_t)k * msn_alpha_rows(g.dc_max) * g.M + pl;
 #pragma unroll
-    for (int u = 0; 2 * u < DC; ++u) {
-      const uint32_t byte = 2 * u < g.dc_max ? alpha[(int64_t)u * g.M] : 0u;
-      ab[2 * u] = byte & 15u;
-      if (2 * u + 1 < DC) ab[2 * u + 1] = byte >> 4;
-    }
-  } else {
-#pragma unroll
-    for (int t = 0; t < DC; ++t) ab[t] = t < g.dc_max ? alpha[(int64_t)t * g.M] : 0u;
+  for (int u = 0; 2 * u < DC; ++u) {
+    const uint32_t byte = 2 * u < g.dc_max ? alpha[(int64_t)u * g.M] : 0u;
+    ab[2 * u] = byte & 15u;
+    if (2 * u + 1 < DC) ab[2 * u + 1] = byte >> 4;
   }
   if (!live) {
     if (bi == 0 && threadIdx.x < 64)
@@ -565,7 +499,7 @@ template <typename Real, int T0, int D, int NW>
 __device__ __forceinline__ void var_edges(const MsnView &g, const MsnWork &w, int k,
                                           const int (&word)[NW], Vec<Real> &s) {
   const Real *m1 = (const Real *)w.m1, *m2 = (const Real *)w.m2;
-  const uint8_t *alpha = w.alpha + (int64_t)k * alpha_rows(g.dc_max) * g.M;
+  const uint8_t *alpha = w.alpha + (int64_t)k * msn_alpha_rows(g.dc_max) * g.M;
   int v[D];
   edge_values<T0, D>(word, g.cx, v);
   bool ok[D];
@@ -578,7 +512,7 @@ __device__ __forceinline__ void var_edges(const MsnView &g, const MsnWork &w, in
     const int rp = ok[t] ? (v[t] & 0xffffff) : 0;
     place[t] = ok[t] ? (v[t] >> 24) : 0;
     ro[t] = el(k, g.M, rp);
-    ai[t] = (uint32_t)(kAlphaNibbles ? place[t] >> 1 : place[t]) * (uint32_t)g.M + (uint32_t)rp;
+    ai[t] = (uint32_t)(place[t] >> 1) * (uint32_t)g.M + (uint32_t)rp;
   }
   MetaWord mt[D];
   uint32_t ab[D];
@@ -586,8 +520,7 @@ __device__ __forceinline__ void var_edges(const MsnView &g, const MsnWork &w, in
 #pragma unroll
   for (int t = 0; t < D; ++t) {
     mt[t] = ld_meta(w.meta + ro[t]);
-    ab[t] = alpha[ai[t]];
-    if constexpr (kAlphaNibbles) ab[t] = (ab[t] >> (4 * (place[t] & 1))) & 15u;
+    ab[t] = (alpha[ai[t]] >> (4 * (place[t] & 1))) & 15u;
     v1[t] = ldv(m1 + ro[t]);
     v2[t] = ldv(m2 + ro[t]);
   }
@@ -621,20 +554,20 @@ __device__ void var_edges_rt(const MsnView &g, const MsnWork &w, int k, const in
 // bytes (8 lanes' decisions, MSB first, :207-219), iterations, and the
 // optional bits / posteriors -- instead of in msn_post / msn_cols.
 template <typename Real, int DV>
-__global__ void __launch_bounds__(256, LDPC_MSN_VAR_MINB) msn_var(MsnView g, MsnWork w, DecodeArgs a, int nb) {
+__global__ void __launch_bounds__(256, 1) msn_var(MsnView g, MsnWork w, DecodeArgs a, int nb) {
   int k, bi;
-  map_block(blockIdx.x, w.chunks, w.nb_var, k, bi, LDPC_MSN_ZIGZAG != 0);
+  map_block(blockIdx.x, w.chunks, w.nb_var, k, bi, true);
   const int m = nb * w.chunks + k;  // the decision's mask buffer
   const uint32_t run = ld_uniform(&w.run[m]), fill = ld_uniform(&w.fill[m]),
                  stop = ld_uniform(&w.stop[m]);
-  const int x = bi * kIB + threadIdx.x;  // column storage position
+  const int x = bi * kMsnIB + threadIdx.x;  // column storage position
   const int64_t ci = el(k, g.N, x);
   Real *LQ = (Real *)w.LQ;
   // the descriptor words and Lci go out together (columns past N load the
   // last column's)
   int word[(DV + 7) / 8];
   desc_words(g.cdesc, bi, g.cs, word);
-  Vec<float> lci = ldv_nt(w.L + el(k, g.N, min(x, g.N - 1)));
+  Vec<float> lci = ldv(w.L + el(k, g.N, min(x, g.N - 1)));
   if (w.out_var && stop) {
     const int lane = threadIdx.x & 63;
     const bool in = x < g.N;
@@ -689,7 +622,7 @@ __global__ void __launch_bounds__(256, LDPC_MSN_VAR_MINB) msn_var(MsnView g, Msn
   Vec<Real> lq;
 #pragma unroll
   for (int f = 0; f < kF; ++f) lq.v[f] = ((fill >> f) & 1u) ? (Real)lci.v[f] : (Real)lci.v[f] + s.v[f];
-  stv_nt(LQ + ci, lq);
+  stv(LQ + ci, lq);
 }
 
 __global__ void msn_init(MsnWork w) {
@@ -709,14 +642,11 @@ __global__ void msn_init(MsnWork w) {
   }
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Pass p reads mask buffer p & 1 and decides into the other.
 template <int PREC>
 void msn_pass(const MsnView &g, const MsnWork &w, const DecodeArgs &a, int par, hipStream_t st) {
   typedef typename Math<PREC>::Real Real;
   const int rblocks = w.nb_check * w.chunks, cblocks = w.nb_var * w.chunks, nb = par ^ 1;
-  static_assert(kMsnFrames == kF, "");
 #define LDPC_MSN_CHECK(DC) \
   msn_check<PREC, DC><<<rblocks, 256, 0, st>>>(g, w, par, a.max_iters, a.et_period, a.B, a.synd)
   if (g.dc_max <= 8)
@@ -742,68 +672,6 @@ void msn_pass(const MsnView &g, const MsnWork &w, const DecodeArgs &a, int par, 
 }
 
 }  // namespace
-
-int msn_default_chunks() {
-  const char *e = getenv("LDPC_MSN_CHUNKS");  // A/B knob
-  const int v = e ? atoi(e) : 0;
-  // 80 chunks of 2 frames = 160 frames in flight, 10 chunks per XCD:
-  // 2 518-2 522 Mbit/s against 2 486 for 64, 2 469 for 96 and 2 104 for 112
-  // (profiles/round4/msn_chunks/; round 3 at 4 frames per chunk: 40 chunks,
-  // profiles/round3/msn/chunks_fused.txt)
-  return v >= 1 ? v : 80;
-}
-
-size_t msn_work_bytes(const MsnView &g, int chunks, int prec) {
-  const size_t real = prec == 1 ? 4 : 8, F = kF, C = chunks;
-  size_t n = al256(C * g.N * F * 4) + al256(C * g.N * F * real);  // L, LQ
-  n += 2 * al256(C * g.M * F * real) + al256(C * g.M * F);        // m1, m2, meta
-  n += al256(C * alpha_rows(g.dc_max) * g.M);                     // alpha
-  n += 5 * al256(C * F * 4);                                      // capsyn, it, frame, out_frame, used
-  n += 4 * al256(2 * C * 4) + al256(C * 9 * 8) + al256(64);      // masks x 2, arrive, ctrl
-  return n;
-}
-
-void msn_work_carve(MsnWork &w, void *base, const MsnView &g, int chunks, int prec) {
-  const size_t real = prec == 1 ? 4 : 8, F = kF, C = chunks;
-  char *p = (char *)base;
-  auto take = [&](size_t bytes) {
-    char *r = p;
-    p += al256(bytes);
-    return (void *)r;
-  };
-  w = MsnWork{};
-  w.chunks = chunks;
-  w.S = chunks * kF;
-  w.real_bytes = (int)real;
-  w.nb_check = (g.M + kIB - 1) / kIB;
-  w.nb_var = (g.N + kIB - 1) / kIB;
-  w.check_waves = w.nb_check * 4;
-  w.out_var = g.out_var;
-  w.L = (float *)take(C * g.N * F * 4);
-  w.LQ = take(C * g.N * F * real);
-  w.m1 = take(C * g.M * F * real);
-  w.m2 = take(C * g.M * F * real);
-  w.meta = (uint8_t *)take(C * g.M * F);
-  w.alpha = (uint8_t *)take(C * alpha_rows(g.dc_max) * g.M);
-  w.capsyn = (int32_t *)take(C * F * 4);
-  w.it = (int32_t *)take(C * F * 4);
-  w.frame = (int32_t *)take(C * F * 4);
-  w.out_frame = (int32_t *)take(C * F * 4);
-  w.used = (int32_t *)take(C * F * 4);
-  w.live = (uint32_t *)take(2 * C * 4);
-  w.run = (uint32_t *)take(2 * C * 4);
-  w.stop = (uint32_t *)take(2 * C * 4);
-  w.fill = (uint32_t *)take(2 * C * 4);
-  w.arrive = (uint64_t *)take(C * 9 * 8);
-  // The decision in the check pass's last block per chunk (12-bit arrival
-  // counts: M <= kMsnMaxRows).  One word per chunk made the 127 blocks of a
-  // chunk contend (check pass 53.5 us against 40.8 + 4.9 for the check and
-  // decision launches, profiles/round3/msn/fused_decide.txt); two levels (8
-  // group words, then the chunk's) measured 2 219-2 229 against 2 207-2 212
-  // Mbit/s for a separate decision launch (profiles/round3/msn/ab_fuse2.txt),
-  // which was then removed
-  w.ctrl = (int32_t *)take(64);
-}
 
 int launch_graph_decode_msn(const MsnView &g, const MsnWork &w, const DecodeArgs &a, int prec,
                             int32_t *h_ctrl, void *stream) {
@@ -844,214 +712,6 @@ int launch_graph_decode_msn(const MsnView &g, const MsnWork &w, const DecodeArgs
   for (int i = 0; i < 2; ++i) (void)hipEventDestroy(ev[i]);
   if (rc == 0 && hipGetLastError() != hipSuccess) rc = -1;
   return rc;
-}
-
-// ---- storage order (host) --------------------------------------------------
-
-namespace {
-
-// Pairs of neighbouring storage rows (columns) of equal degree whose t-th
-// edges land on neighbouring storage columns (rows): the contiguity a wave's
-// gathers get from the order.
-long contiguity(const MsnTables &t) {
-  long s = 0;
-  const int M = (int)t.rp.size() - 1, N = (int)t.cp.size() - 1;
-  for (int p = 0; p + 1 < M; ++p) {
-    const int d = t.rp[p + 1] - t.rp[p];
-    if (t.rp[p + 2] - t.rp[p + 1] != d) continue;
-    for (int e = 0; e < d; ++e) s += t.rcs[(size_t)e * M + p + 1] == t.rcs[(size_t)e * M + p] + 1;
-  }
-  for (int x = 0; x + 1 < N; ++x) {
-    const int d = t.cp[x + 1] - t.cp[x];
-    if (t.cp[x + 2] - t.cp[x + 1] != d) continue;
-    for (int e = 0; e < d; ++e)
-      s += (t.crs[(size_t)e * N + x + 1] & 0xffffff) == (t.crs[(size_t)e * N + x] & 0xffffff) + 1;
-  }
-  return s;
-}
-
-}  // namespace
-
-// A slot-major table full[t][x] (D x n, -1 past each item's degree) as
-// descriptors (MsnDesc: up to 4 runs of consecutive values): S = D per wave
-// of the kernels' 256-item blocks, slot t of wave w of block b at
-// (4 b + w) S + t; slots past the block's largest degree hold no edge.  Each
-// descriptor also carries that degree (pad[0]) and whether its wave's values
-// are explicit (pad[1]): a wave with a slot of more than 4 runs keeps every
-// slot's 64 values in `x` (at each descriptor's xoff).
-void msn_block_tables(const std::vector<int32_t> &full, int D, int n, std::vector<MsnDesc> &desc,
-                      std::vector<int32_t> &x) {
-  const int nb = (n + kIB - 1) / kIB, nw = kIB / 64, S = D;
-  MsnDesc none{};
-  for (int r = 0; r < 4; ++r) none.b[r] = kMsnNoEdge;
-  none.thr = 64u | 64u << 8 | 64u << 16;
-  none.xoff = -1;
-  desc.assign((size_t)nb * nw * S, none);
-  x.clear();
-  for (int b = 0; b < nb; ++b) {
-    int deg = 0;
-    for (int i = 0; i < kIB; ++i) {
-      const int c = b * kIB + i;
-      if (c >= n) break;
-      for (int t = 0; t < D; ++t)
-        if (full[(size_t)t * n + c] != -1) deg = std::max(deg, t + 1);
-    }
-    for (int w = 0; w < nw; ++w) {
-      MsnDesc *mine = &desc[((size_t)b * nw + w) * S];
-      std::vector<int32_t> vals((size_t)deg * 64);
-      bool explicit_wave = false;
-      for (int t = 0; t < deg; ++t) {
-        int32_t *v = &vals[(size_t)t * 64];
-        for (int l = 0; l < 64; ++l) {
-          const int c = b * kIB + w * 64 + l;
-          v[l] = c < n ? full[(size_t)t * n + c] : -1;
-        }
-        int start[64], runs = 0;
-        for (int l = 0; l < 64; ++l) {
-          const bool cont = l > 0 && ((v[l - 1] < 0 && v[l] < 0) || (v[l - 1] >= 0 && v[l] == v[l - 1] + 1));
-          if (!cont) start[runs++] = l;
-        }
-        MsnDesc &d = mine[t];
-        explicit_wave |= runs > 4;
-        uint32_t thr = 0;
-        for (int r = 0; r < 4; ++r) {
-          const int a = r < runs ? start[r] : 64;
-          d.b[r] = r < runs ? (v[a] < 0 ? kMsnNoEdge : v[a] - a) : kMsnNoEdge;
-          if (r >= 1) thr |= (uint32_t)a << (8 * (r - 1));
-        }
-        d.thr = thr;
-      }
-      if (explicit_wave)
-        for (int t = 0; t < deg; ++t) mine[t].xoff = (int32_t)(x.size() + (size_t)t * 64);
-      if (explicit_wave) x.insert(x.end(), vals.begin(), vals.end());
-      for (int t = 0; t < S; ++t) {
-        mine[t].pad[0] = deg;
-        mine[t].pad[1] = explicit_wave ? 1 : 0;
-      }
-    }
-  }
-  // self-check: decode every (block, wave, slot, lane) as the kernels do
-  // (desc_words / slot_value / slot_explicit) and compare with the table
-  for (int b = 0; b < nb; ++b)
-    for (int w = 0; w < nw; ++w)
-      for (int t = 0; t < S; ++t) {
-        const MsnDesc *mine = &desc[((size_t)b * nw + w) * S];
-        const MsnDesc &d = mine[t];
-        const int deg = mine[0].pad[0];
-        const bool expl = mine[0].pad[1] != 0;
-        for (int l = 0; l < 64; ++l) {
-          const int c = b * kIB + w * 64 + l;
-          const int32_t want = c < n ? full[(size_t)t * n + c] : -1;
-          int32_t got;
-          if (t >= deg) {
-            got = -1;
-          } else if (expl) {
-            got = x[(size_t)d.xoff + l];
-          } else {
-            int base = l >= (int)(d.thr & 0xffu) ? d.b[1] : d.b[0];
-            base = l >= (int)((d.thr >> 8) & 0xffu) ? d.b[2] : base;
-            base = l >= (int)((d.thr >> 16) & 0xffu) ? d.b[3] : base;
-            got = base + l;
-          }
-          if ((want < 0) != (got < 0) || (want >= 0 && want != got))
-            throw std::runtime_error("msn_block_tables: descriptor self-check failed");
-        }
-      }
-}
-
-// Storage-ordered tables of H (rows rpos, columns cpos): row offsets and
-// column offsets for the degrees, and slot-major edge lists -- rcs[t][p] the
-// storage column of row p's t-th edge (ascending original column), crs[t][x]
-// the storage row of column x's t-th edge (ascending original row) | the
-// edge's place in that row << 24 -- so a wave's t-th edges are one
-// coalesced load.
-void msn_tables(int M, int N, const std::vector<int32_t> &rp0, const std::vector<int32_t> &ci0,
-                const std::vector<int32_t> &rpos, const std::vector<int32_t> &cpos,
-                MsnTables &t) {
-  std::vector<int32_t> rorig(M), corig(N);
-  for (int j = 0; j < M; ++j) rorig[rpos[j]] = j;
-  for (int c = 0; c < N; ++c) corig[cpos[c]] = c;
-  int dc = 0, dv = 0;
-  std::vector<int32_t> cdeg((size_t)N, 0);
-  for (int j = 0; j < M; ++j) {
-    dc = std::max(dc, rp0[j + 1] - rp0[j]);
-    for (int32_t o = rp0[j]; o < rp0[j + 1]; ++o) cdeg[cpos[ci0[o]]]++;
-  }
-  for (int x = 0; x < N; ++x) dv = std::max(dv, cdeg[x]);
-  t.rp.assign((size_t)M + 1, 0);
-  t.rcs.assign((size_t)dc * M, -1);
-  for (int p = 0; p < M; ++p) {
-    const int j = rorig[p];
-    t.rp[p + 1] = t.rp[p] + (rp0[j + 1] - rp0[j]);
-    for (int32_t o = rp0[j]; o < rp0[j + 1]; ++o) t.rcs[(size_t)(o - rp0[j]) * M + p] = cpos[ci0[o]];
-  }
-  t.cp.assign((size_t)N + 1, 0);
-  for (int x = 0; x < N; ++x) t.cp[x + 1] = t.cp[x] + cdeg[x];
-  t.crs.assign((size_t)dv * N, -1);
-  std::vector<int32_t> fill((size_t)N, 0);
-  for (int j = 0; j < M; ++j)  // original rows ascending
-    for (int32_t o = rp0[j]; o < rp0[j + 1]; ++o) {
-      const int x = cpos[ci0[o]];
-      t.crs[(size_t)fill[x]++ * N + x] = rpos[j] | ((o - rp0[j]) << 24);
-    }
-  t.corig = corig;
-  t.cpos = cpos;
-  t.rpos = rpos;
-  msn_block_tables(t.rcs, dc, M, t.rdesc, t.rx);
-  msn_block_tables(t.crs, dv, N, t.cdesc, t.cx);
-  t.rs = dc;
-  t.cs = dv;
-  // outputs from the variable pass need the info columns in place, 8 per byte
-  t.out_var = M % 8 == 0;
-  for (int c = M; c < N && t.out_var; ++c) t.out_var = cpos[c] == c;
-}
-
-// Chooses the storage order: the identity, or for M a multiple of 360 the
-// DVB-S2 residue-class order (row r -> (r mod q) * 360 + r / q, q = M / 360,
-// and the staircase's degree <= 2 columns {r, r+1} moved among their own
-// positions in the order of r's class position) -- whichever gives the
-// kernels' gathers more contiguity.  LDPC_MSN_ORDER=0 / 1 forces one.
-void msn_build(int M, int N, const std::vector<int32_t> &rp0, const std::vector<int32_t> &ci0,
-               MsnTables &t) {
-  std::vector<int32_t> rid(M), cid(N);
-  for (int j = 0; j < M; ++j) rid[j] = j;
-  for (int c = 0; c < N; ++c) cid[c] = c;
-  const char *env = getenv("LDPC_MSN_ORDER");
-  const int force = env ? atoi(env) : -1;
-  msn_tables(M, N, rp0, ci0, rid, cid, t);
-  t.order = 0;
-  t.score[0] = contiguity(t);
-  t.score[1] = -1;
-  if (M % 360 != 0 || force == 0) return;
-  const int q = M / 360;
-  std::vector<int32_t> rpos(M), cpos(cid);
-  for (int j = 0; j < M; ++j) rpos[j] = (j % q) * 360 + j / q;
-  // staircase columns: degree 1 or 2 with rows r (and r + 1)
-  std::vector<int32_t> cdeg(N, 0), cfirst(N, -1), clast(N, -1);
-  for (int j = 0; j < M; ++j)
-    for (int32_t o = rp0[j]; o < rp0[j + 1]; ++o) {
-      const int c = ci0[o];
-      if (cfirst[c] < 0) cfirst[c] = j;
-      clast[c] = j;
-      cdeg[c]++;
-    }
-  std::vector<int32_t> stair, slots;
-  for (int c = 0; c < N; ++c)
-    if ((cdeg[c] == 1) || (cdeg[c] == 2 && clast[c] == cfirst[c] + 1)) {
-      stair.push_back(c);
-      slots.push_back(c);
-    }
-  std::stable_sort(stair.begin(), stair.end(),
-                   [&](int a, int b) { return rpos[cfirst[a]] < rpos[cfirst[b]]; });
-  for (size_t i = 0; i < stair.size(); ++i) cpos[stair[i]] = slots[i];
-  MsnTables qc;
-  msn_tables(M, N, rp0, ci0, rpos, cpos, qc);
-  qc.order = 1;
-  const long s_id = contiguity(t), s_qc = contiguity(qc);
-  qc.score[0] = s_id;
-  qc.score[1] = s_qc;
-  t.score[1] = s_qc;
-  if (force == 1 || s_qc > s_id) t = std::move(qc);
 }
 
 }  // namespace ldpc

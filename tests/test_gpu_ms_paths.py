@@ -62,6 +62,34 @@ def test_batches_and_et_period(gdec, B):
             np.testing.assert_array_equal(out[k], ref[k], err_msg="%s et=%d" % (k, et))
 
 
+@pytest.mark.parametrize("method,precision", [(0, 0), (0, 1), (1, 0)],
+                         ids=["minsum-f64", "minsum-f32", "sumproduct-f64"])
+def test_work_limit_lowers_chunks_and_groups(gdec, method, precision):
+    """ldpc_set_work_limit(1): no workspace fits, so the pipeline lowers its
+    chunk count to the one chunk it always keeps (two frames in flight, every
+    slot recycled 32 times over 65 frames) and the other path decodes in
+    groups of 64 frames (64 + 1).  Every output equals the oracle's -- for f32
+    its float restatement's."""
+    from oracle import oracle as orc
+    B = 65
+    rng = np.random.default_rng(B)
+    Hr = gdec.H
+    x = 2.0 * __import__("ldpc_ece535a").encode(
+        Hr, rng.integers(0, 2, size=(B, 32), dtype=np.uint8)) - 1.0
+    db = rng.integers(0, 5, size=B)
+    y = (x + np.sqrt(10.0 ** (-db / 10.0))[:, None] * rng.standard_normal(x.shape)).astype(
+        np.float32)
+    kw = {"real": "f32"} if precision == 1 else {}
+    ref = orc.decode_batch(method, Hr, y, 50, nthreads=16, et_period=1, **kw)
+    gdec.set_work_limit(1)
+    try:
+        out = gdec.decode(y, method=method, max_iters=50, et_period=1, precision=precision)
+    finally:
+        gdec.set_work_limit(0)
+    for k in ("bits", "packed", "iters", "synd"):
+        np.testing.assert_array_equal(out[k], ref[k], err_msg=k)
+
+
 def test_non_finite(gdec):
     from oracle import oracle as orc
     rng = np.random.default_rng(3)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Per-kernel time and counters of one rocprofv3 run directory (as written by
-tools/profile_msn.sh): total / mean duration per kernel name from the kernel
+"""Per-kernel time and counters of one rocprofv3 run directory (a kernel trace
+under kt/, counter runs under pmc*/): total / mean duration per kernel name from the kernel
 trace, and the sum and mean per dispatch of every PMC counter per kernel.
 
 usage: tools/kernel_split.py gpurun_out/prof/msn_2 [--decodes N]
