@@ -909,14 +909,31 @@ int ldpc_set_work_limit(ldpc_ctx *ctx, int64_t bytes);
 int ldpc_encode_device(ldpc_ctx *ctx, const uint8_t *d_data_bits, int B,
                        uint8_t *d_codewords, void *hip_stream);
 
-/* n bytes of seeded pseudo-random bits 0/1 (Philox4x32-10; the same seed
- * gives the same bits).  Current device; NULL stream = the null stream.
- * Errors: ldpc_last_error(NULL). */
+/* The two draws below share one layout (tests/channel_ref.py restates it,
+ * tests/test_gpu_channel.py holds the kernels to it).  Samples 4c .. 4c+3 come
+ * from one Philox4x32-10 block (Salmon et al., SC'11; Random123's constants):
+ *   counter = (c & 0xFFFFFFFF, c >> 32, stream, 0x2545F491),  c = i >> 2
+ *   key     = (seed & 0xFFFFFFFF, seed >> 32)
+ *   stream  = 1 for ldpc_random_bits, 2 for ldpc_bpsk_awgn
+ * so the noise of a seed is independent of that seed's bits, a draw of n
+ * samples is a prefix of any longer one, and both words of the seed count. */
+
+/* n bytes of seeded pseudo-random bits 0/1: byte i is bit 31 of word i & 3 of
+ * its block (the same seed gives the same bits).  Current device; NULL stream
+ * = the null stream.  n = 0 writes nothing.  Errors: ldpc_last_error(NULL). */
 int ldpc_random_bits(uint8_t *d_out, int64_t n, uint64_t seed, void *hip_stream);
 
-/* BPSK + AWGN: d_out[i] = (2 d_bits[i] - 1) + sigma * n_i, n_i ~ N(0,1)
- * (Philox + Box-Muller, seeded); sigma = sqrt(10^(-EbN0/10)) reproduces the
- * reference's convention (apps/ldpc_lapack.cpp:629-636). */
+/* BPSK + AWGN: d_out[i] = (2 (d_bits[i] & 1) - 1) + sigma * n_i, n_i ~ N(0,1),
+ * sigma >= 0; sigma = sqrt(10^(-EbN0/10)) reproduces the reference's
+ * convention (apps/ldpc_lapack.cpp:629-636).  Box-Muller in float on the
+ * block's words (x, y, z, w): pair a from (x, y), pair b from (z, w),
+ *   u1 = min((float(x) + 1) * 2^-32, 1) in (0, 1],  u2 = float(y) * 2^-32 in [0, 1]
+ *   r = sqrtf(-2 logf(u1)),  n[4c] = ra cospi(2 u2a),  n[4c+1] = ra sinpi(2 u2a),
+ *   n[4c+2] = rb cospi(2 u2b),  n[4c+3] = rb sinpi(2 u2b).
+ * u1 >= 2^-32, so |n_i| <= sqrt(64 ln 2) = 6.66: the tails end at 6.66 sigma.
+ * The sum is two roundings, fl(fl(2b - 1) + fl(sigma * n_i)) (the library is
+ * built without contraction); the deviates are within 3.2 float ulps of the
+ * real-valued formula on an MI355X (profiles/round25/channel.txt). */
 int ldpc_bpsk_awgn(const uint8_t *d_bits, int64_t n, float sigma, uint64_t seed,
                    float *d_out, void *hip_stream);
 
