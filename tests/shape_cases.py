@@ -10,6 +10,9 @@ decoded on and the oracle's results for them (computed once per process).
 tests/test_shape_cases.py checks on the CPU that the table covers the
 dispatch; tests/test_gpu_shapes.py runs it on the device.
 
+No code here has a column of degree > M / 2, so bit flipping (method 2) never
+flips on this table: tests/bitflip_cases.py is the table for that.
+
 When a dispatch cell is added (another slot count, loop length or degree
 body), restate it in kernel_shape / graph_bodies below and add a case here:
 the coverage test fails until the table reaches it."""
